@@ -17,6 +17,13 @@ exits with its status.  Default N > 1 mode: weak scaling, every rank processes i
 data-path collective except the final all-gather of ids + scores.  `--global-batch G` (BASELINE config 4:
 G = 2048 over 8 GPUs): strong scaling, rank r takes the contiguous shard `shard_bounds(G, r, N)`.
 
+A plain run does only what the headline figure needs: set-up, warm-up (with the measured choice of the decode
+schedule), ONE timed window of exactly `--steps` steps, the outputs of its last step under `--dump-outputs DIR`, the line.
+`--full` adds everything else the benchmark measures or checks: `--repeat` windows (at least 1 s in all), the untimed
+pre-pass (encode / decode split, solo decode), the roofline of the dominant kernel class (events in the timed steps), the
+bit-exact check of every pipelined step against the solo pass, the CPU baseline, parity against the oracle and the
+fp32 mode, and the other precisions' pipelined rates (`also_pipelined`).
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).
 """
 from __future__ import annotations
@@ -40,6 +47,7 @@ POS = (252 * 56, 126 * 28, 63 * 14, 31 * 7)  # positions per 10 s clip and stage
 PEAK_BF16_TFLOPS = 2500.0                    # dense MFMA bf16 (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0                        # HBM3E spec (MI355X_MICROARCH.md)
 DEC_GROUP_DEFAULT = 16                       # CN_DEC_GROUP: batches whose beam searches run as one chain (see step_grouped)
+TRIAL_STEPS = 48                             # steps per window of the decode-schedule trial in a plain run (--full: --steps)
 FUSED_STAGES = (0, 1, 2)                     # pw1 + GELU + pw2 run as ONE kernel (mlp_rc2.h), timed under "pw1_gemm"
 # kernel-name fragments of each profiling class in the committed PMC tables (profiles/*_pmc_*.csv)
 PMC_KERNELS = {
@@ -58,14 +66,20 @@ def parse_args(argv=None):
     ap.add_argument("--global-batch", type=int, default=0, help="total clips, sharded over the GPUs (strong scaling)")
     ap.add_argument("--beam", type=int, default=3)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f16", "bf16+f16dec", "mixed", "mixed16", "fp32", "exact"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: repeated windows, pre-pass, roofline, pipelined-vs-solo check, CPU baseline, "
+                         "parity legs, other precisions (a plain run times one window of exactly --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (caption ids, scores; tag probabilities "
+                         "on one GPU) as float32 DIR/<name>.npy")
     ap.add_argument("--repeat", type=int, default=5,
-                    help="timed windows of --steps steps each (barrier + synchronize around every window); `value` and "
+                    help="--full: timed windows of --steps steps each (barrier + synchronize around every window); `value` and "
                          "`ms_per_step` are the MEDIAN window's, every window's clips/s is listed under `windows`")
     ap.add_argument("--workload", default="fixed", choices=["fixed", "mixed"],
                     help="fixed: 10 s clips; mixed: lengths U[1 s, 30 s] (seed 1234), length-bucketed batches")
-    ap.add_argument("--cpu-clips", type=int, default=32, help="clips in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-clips", type=int, default=32, help="--full: clips in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--parity-clips", type=int, default=64, help="clips in the bf16-vs-fp32 agreement leg (0 = skip)")
+    ap.add_argument("--parity-clips", type=int, default=64, help="--full: clips in the bf16-vs-fp32 agreement leg (0 = skip)")
     ap.add_argument("--parity-batches", type=int, default=4,
                     help="batches of --parity-clips clips (other seeds) in the agreement-with-the-fp32-mode leg: an identical-caption rate "
                          "moves by several clips when a kernel's fp32 rounding changes in the last bit, 64 clips are a noisy sample")
@@ -73,7 +87,7 @@ def parse_args(argv=None):
                     help="gloo: CPU self-test of the launcher / sharding / gather path (no GPU work, no timing)")
     ap.add_argument("--master-port", type=int, default=0)
     ap.add_argument("--also", default="bf16:e2,bf16:g1,bf16+f16dec,f16,mixed16,exact,certified,certified@peaked,certified-best@peaked,certified:f16@peaked",
-                    help="N = 1, fixed workload, bf16 only: after the run, the SAME pipelined benchmark at these precisions (one child "
+                    help="--full, N = 1, fixed workload, bf16 only: after the run, the SAME pipelined benchmark at these precisions (one child "
                          "process each, 3 windows, no CPU / parity legs), reported under `also_pipelined` ('' = skip); `PREC:g1` = that "
                          "precision with one beam search per batch (CN_DEC_GROUP=1) instead of the grouped decode")
     return ap.parse_args(argv)
@@ -313,6 +327,25 @@ def compare_ids(got, got_lp, ref, ref_lp=None, margins=None):
     return r
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # --dump-outputs: array bytes in all (below 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as float32 out_dir/<name>.npy.  The arrays share their first (clip) axis; above
+    DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of clips is kept from each (its indices in rows.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = next(iter(arrs.values())).shape[0]
+    row_bytes = sum(a.nbytes for a in arrs.values()) / max(n, 1)
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, max(1, int(DUMP_LIMIT_BYTES // (row_bytes + 4))), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float32)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def also_pipelined(args, batch):
     """The same encode | decode | decode pipeline at other precisions, each in a child process of its own (this process stays
     idle meanwhile; a child is a plain `python bench.py --precision P`, started, never exec'ed into).  `value` of the line stays
@@ -343,7 +376,7 @@ def also_pipelined(args, batch):
         if opt == "e2":                        # "bf16:e2" = the encodes of consecutive batches on TWO streams (see s_encs in main)
             env["CN_ENC_STREAMS"] = "2"
         cmd = [sys.executable, os.path.abspath(__file__), "--precision", prec, "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--repeat", "3", "--batch", str(batch), "--beam", str(args.beam), "--cpu-clips", "0", "--parity-clips", "0", "--also", ""]
+               "--repeat", "3", "--batch", str(batch), "--beam", str(args.beam), "--cpu-clips", "0", "--parity-clips", "0", "--also", "", "--full"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
             d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -719,6 +752,7 @@ def main() -> None:
                 pe[1].record(s_enc)
             eng.encode(waves[i % NB], out=(gs["fe"][m * B:(m + 1) * B], gs["clip"]), slot=i & 1)
             gs["enc_done"][m].record(s_enc)
+            state["last_clips"] = [gs["clip"]]   # this step's tag probabilities (B, 527)
             if probe is not None:
                 pe[2].record(s_enc)
                 probe.append((m, pe))
@@ -754,8 +788,10 @@ def main() -> None:
         keep = state.get("keep") if (state.get("keep") is not None and i < state["keep"][0].shape[0]) else None
         if state.get("prof") is not None:
             eng.profile_enable(state["prof"] if i % prof_every == 0 else ())
+        state["last_clips"] = []             # this step's tag probabilities, bucket by bucket (the row order of lp_s)
         for k, (w_, lens_, t_) in enumerate(batches):
             sl = slots[n_slot * k + (i % n_slot)]
+            state["last_clips"].append(sl["clip"])
             bos = bos_dev[k]
             s_enc = s_encs[i % len(s_encs)]
             s_dec = s_decs[(i * len(batches) + k) % n_dec]   # consecutive buckets decode on different streams
@@ -806,8 +842,11 @@ def main() -> None:
     # per G batches (the rule's G) and one search per batch -- run their warm-up and two untimed windows of --steps steps; the
     # faster one (by its better window; over all ranks: the slowest rank's) is kept and both rates go into the JSON line.
     # CN_DEC_GROUP set explicitly (or CN_SCHED_TRIAL=0) skips the trial.
+    # A plain run keeps the trial's windows to at most TRIAL_STEPS steps (a multiple of G), so that its cost does not grow with --steps.
     schedule = None
     if args.workload == "fixed" and G > 1 and os.environ.get("CN_DEC_GROUP") is None and os.environ.get("CN_SCHED_TRIAL", "1") != "0":
+        trial_steps = args.steps if args.full else min(args.steps, max(1, TRIAL_STEPS // G) * G)
+
         def trial(fn, warm):
             state["i"] = 0
             for _ in range(warm):
@@ -816,7 +855,7 @@ def main() -> None:
             best_dt = float("inf")
             for _ in range(2):
                 t0_ = time.perf_counter()
-                for _ in range(args.steps):
+                for _ in range(trial_steps):
                     fn()
                 torch.cuda.synchronize(dev)
                 best_dt = min(best_dt, time.perf_counter() - t0_)
@@ -827,8 +866,8 @@ def main() -> None:
             tt = torch.tensor([t_grouped, t_single], dtype=torch.float64, device=cdev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             t_grouped, t_single = float(tt[0]), float(tt[1])
-        schedule = {"candidates": {f"G{G}x{n_decg}": round(total_clips * args.steps / t_grouped, 1),
-                                   f"G1x{n_dec}": round(total_clips * args.steps / t_single, 1)},
+        schedule = {"candidates": {f"G{G}x{n_decg}": round(total_clips * trial_steps / t_grouped, 1),
+                                   f"G1x{n_dec}": round(total_clips * trial_steps / t_single, 1)},
                     "unit": "clips/s (better of two untimed windows)", "rule_G": G}
         if t_single < t_grouped:
             G = 1
@@ -840,74 +879,76 @@ def main() -> None:
     for _ in range(warm_used):
         step()
     fence()
-    # The timed region is at least CN_MIN_TIMED_S (1 s) long whoever calls: `--steps` stays what the caller passed, the number of
-    # windows is raised from `--repeat` until steps x windows fill that time (the driver's --steps 20 gave five
-    # 98 ms windows).  One untimed window measures the step; every rank takes the slowest rank's estimate.
-    t_est = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize(dev)
-    t_est = time.perf_counter() - t_est
-    if world > 1:
-        te_ = torch.tensor([t_est], dtype=torch.float64, device=cdev)
-        dist.all_reduce(te_, op=dist.ReduceOp.MAX)
-        t_est = float(te_[0])
-    fence()
-    min_timed_s = float(os.environ.get("CN_MIN_TIMED_S", "1.0"))
-    repeat_used = max(1, args.repeat, min(64, int(math.ceil(min_timed_s / max(t_est, 1e-6)))))
-
-    # ---- pre-pass (untimed): which kernel class dominates, encode / decode split --------------------
     w0, lens0, t0_ = batches[0]
     B0 = w0.shape[0]
     bos0 = bos_dev[0]
-    enc_classes = ("frontend", "stem", "dwconv_ln", "pw1_gemm", "pw2_gemm", "downsample", "heads")
-    eng.profile_enable(enc_classes)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    ev[0].record()
-    eng.encode(w0, out=(slots[0]["fe"], slots[0]["clip"]))     # (straight behind the warm-up steps: the chip is at its working clock)
-    ev[1].record()
-    if G > 1:   # (the grouped pipeline never ran the one-batch search: two calls so that the timed one below replays its graph)
-        for _ in range(2):
-            eng.decode(slots[0]["fe"], lens0, bos0, forbid, beam, min_pred, max_pred, clone=False, slot=0)
-    ev[2].record()
-    out = eng.decode(slots[0]["fe"], lens0, bos0, forbid, beam, min_pred, max_pred, clone=False, slot=0)
-    ev[3].record()
-    torch.cuda.synchronize(dev)
-    pre = eng.profile_read()
-    eng.profile_enable(())
-    encode_ms, decode_ms = ev[0].elapsed_time(ev[1]), ev[2].elapsed_time(ev[3])
-    stage_ms = {k: round(v[0], 4) for k, v in pre.items()}
-    dominant = max(("pw1_gemm", "pw2_gemm", "dwconv_ln"), key=lambda k: pre.get(k, (0.0, 0))[0])
-    solo_preds, solo_lps = out["best_preds"].clone(), out["best_lprobs"].clone()  # un-pipelined result of batch 0
-    solo_rot_p, solo_rot_l = [solo_preds], [solo_lps]       # un-pipelined results of every batch of the rotation
-    for k_ in range(1, NB):
-        eng.encode(waves[k_], out=(slots[0]["fe"], slots[0]["clip"]))
-        o_ = eng.decode(slots[0]["fe"], lens0, bos0, forbid, beam, min_pred, max_pred, clone=False, slot=0)
-        solo_rot_p.append(o_["best_preds"].clone())
-        solo_rot_l.append(o_["best_lprobs"].clone())
-    solo_rot_p, solo_rot_l = torch.stack(solo_rot_p), torch.stack(solo_rot_l)      # (NB, B, max_pred), (NB, B)
-    if NB > 1:   # (the pre-pass below and the parity legs work on batch 0: its frame embeddings back into slot 0)
-        eng.encode(w0, out=(slots[0]["fe"], slots[0]["clip"]))
-    bm = int(out["sizes"][1].item())
-    best = out["best_preds"][:, :bm]
-    best_tokens = int((best != 0).sum().item())            # tokens of the returned captions (<eos> included)
-    beam_tokens = int((out["mult_preds"] != 0).sum().item())  # row-steps of every hypothesis of the search
-    decode_ms_grouped = graph_nodes_grouped = None
-    if G > 1:   # the chain the pipeline actually runs: G batches per beam search, solo, replayed from its graph
-        gs0 = gslots[0]
-        for m_ in range(G):
-            gs0["fe"][m_ * B:(m_ + 1) * B].copy_(slots[0]["fe"])
-        evg = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        evg[0].record()
-        og = eng.decode(gs0["fe"], lens_big, bos_big, forbid, beam, min_pred, max_pred, clone=False, slot=100)
-        evg[1].record()
+    repeat_used, min_timed_s, dominant = 1, None, None   # (a plain run: one window of --steps steps, no pre-pass)
+    if args.full:
+        # The timed region is at least CN_MIN_TIMED_S (1 s) long whoever calls: `--steps` stays what the caller passed, the number of
+        # windows is raised from `--repeat` until steps x windows fill that time (the driver's --steps 20 gave five
+        # 98 ms windows).  One untimed window measures the step; every rank takes the slowest rank's estimate.
+        t_est = time.perf_counter()
+        for _ in range(args.steps):
+            step()
         torch.cuda.synchronize(dev)
-        decode_ms_grouped = evg[0].elapsed_time(evg[1])
-        graph_nodes_grouped = eng.decode_graph_nodes()
-        # (the grouped search returns, for each of its G copies of batch 0, exactly the solo search's captions and scores)
-        if not (torch.equal(og["best_preds"].view(G, B, -1), solo_preds[None].expand(G, -1, -1)) and
-                torch.equal(og["best_lprobs"].view(G, B), solo_lps[None].expand(G, -1))):
-            raise SystemExit("bench: the grouped beam search returned other captions than the search of one batch")
+        t_est = time.perf_counter() - t_est
+        if world > 1:
+            te_ = torch.tensor([t_est], dtype=torch.float64, device=cdev)
+            dist.all_reduce(te_, op=dist.ReduceOp.MAX)
+            t_est = float(te_[0])
+        fence()
+        min_timed_s = float(os.environ.get("CN_MIN_TIMED_S", "1.0"))
+        repeat_used = max(1, args.repeat, min(64, int(math.ceil(min_timed_s / max(t_est, 1e-6)))))
+
+        # ---- pre-pass (untimed): which kernel class dominates, encode / decode split --------------------
+        enc_classes = ("frontend", "stem", "dwconv_ln", "pw1_gemm", "pw2_gemm", "downsample", "heads")
+        eng.profile_enable(enc_classes)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        eng.encode(w0, out=(slots[0]["fe"], slots[0]["clip"]))     # (straight behind the warm-up steps: the chip is at its working clock)
+        ev[1].record()
+        if G > 1:   # (the grouped pipeline never ran the one-batch search: two calls so that the timed one below replays its graph)
+            for _ in range(2):
+                eng.decode(slots[0]["fe"], lens0, bos0, forbid, beam, min_pred, max_pred, clone=False, slot=0)
+        ev[2].record()
+        out = eng.decode(slots[0]["fe"], lens0, bos0, forbid, beam, min_pred, max_pred, clone=False, slot=0)
+        ev[3].record()
+        torch.cuda.synchronize(dev)
+        pre = eng.profile_read()
+        eng.profile_enable(())
+        encode_ms, decode_ms = ev[0].elapsed_time(ev[1]), ev[2].elapsed_time(ev[3])
+        stage_ms = {k: round(v[0], 4) for k, v in pre.items()}
+        dominant = max(("pw1_gemm", "pw2_gemm", "dwconv_ln"), key=lambda k: pre.get(k, (0.0, 0))[0])
+        solo_preds, solo_lps = out["best_preds"].clone(), out["best_lprobs"].clone()  # un-pipelined result of batch 0
+        solo_rot_p, solo_rot_l = [solo_preds], [solo_lps]       # un-pipelined results of every batch of the rotation
+        for k_ in range(1, NB):
+            eng.encode(waves[k_], out=(slots[0]["fe"], slots[0]["clip"]))
+            o_ = eng.decode(slots[0]["fe"], lens0, bos0, forbid, beam, min_pred, max_pred, clone=False, slot=0)
+            solo_rot_p.append(o_["best_preds"].clone())
+            solo_rot_l.append(o_["best_lprobs"].clone())
+        solo_rot_p, solo_rot_l = torch.stack(solo_rot_p), torch.stack(solo_rot_l)      # (NB, B, max_pred), (NB, B)
+        if NB > 1:   # (the pre-pass below and the parity legs work on batch 0: its frame embeddings back into slot 0)
+            eng.encode(w0, out=(slots[0]["fe"], slots[0]["clip"]))
+        bm = int(out["sizes"][1].item())
+        best = out["best_preds"][:, :bm]
+        best_tokens = int((best != 0).sum().item())            # tokens of the returned captions (<eos> included)
+        beam_tokens = int((out["mult_preds"] != 0).sum().item())  # row-steps of every hypothesis of the search
+        decode_ms_grouped = graph_nodes_grouped = None
+        if G > 1:   # the chain the pipeline actually runs: G batches per beam search, solo, replayed from its graph
+            gs0 = gslots[0]
+            for m_ in range(G):
+                gs0["fe"][m_ * B:(m_ + 1) * B].copy_(slots[0]["fe"])
+            evg = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            evg[0].record()
+            og = eng.decode(gs0["fe"], lens_big, bos_big, forbid, beam, min_pred, max_pred, clone=False, slot=100)
+            evg[1].record()
+            torch.cuda.synchronize(dev)
+            decode_ms_grouped = evg[0].elapsed_time(evg[1])
+            graph_nodes_grouped = eng.decode_graph_nodes()
+            # (the grouped search returns, for each of its G copies of batch 0, exactly the solo search's captions and scores)
+            if not (torch.equal(og["best_preds"].view(G, B, -1), solo_preds[None].expand(G, -1, -1)) and
+                    torch.equal(og["best_lprobs"].view(G, B), solo_lps[None].expand(G, -1))):
+                raise SystemExit("bench: the grouped beam search returned other captions than the search of one batch")
 
     # ---- timed region: R windows of exactly K steps each, events only around the dominant class ---------
     # (every window is bracketed by barrier + synchronize on both sides; the reported value is the MEDIAN window's)
@@ -919,13 +960,14 @@ def main() -> None:
     prof_every = max(1, int(os.environ.get("CN_PROF_EVERY", "5")))
     while prof_every > 1 and math.gcd(prof_every, G) > 1:
         prof_every += 1
-    state["prof"] = (dominant,)
+    state["prof"] = (dominant,) if args.full else None
     state["i"] = 0
     n_rep = repeat_used
     n_timed = n_rep * args.steps
-    n_keep = n_timed if (world > 1 or os.environ.get("CN_BENCH_CHECK_ALL", "1") != "0") else 0  # (0: only the last step is compared)
-    state["keep"] = (torch.zeros((n_keep, B, solo_preds.shape[1]), dtype=solo_preds.dtype, device=dev),
-                     torch.zeros((n_keep, B), dtype=solo_lps.dtype, device=dev))
+    # (N > 1: the gather reads the keep tables; N = 1: they serve the --full check only, 0 = only the last step is compared)
+    n_keep = n_timed if (world > 1 or (args.full and os.environ.get("CN_BENCH_CHECK_ALL", "1") != "0")) else 0
+    state["keep"] = (torch.zeros((n_keep, B, max_pred), dtype=torch.int32, device=dev),
+                     torch.zeros((n_keep, B), dtype=torch.float32, device=dev))
     win_dt, own_dt, issue_dt = [], [], []
     gathered = None
     if os.environ.get("CN_GAP_PROBE") and G > 1:   # lab: where the encode stream idles (stderr; events around every encode)
@@ -955,51 +997,60 @@ def main() -> None:
             a_ = np.array(rows_)
             print(f"[bench] gap probe m={m_}: after previous encode {a_[:, 0].mean() * 1e3:.0f} us (max {a_[:, 0].max() * 1e3:.0f}), "
                 f"waiting for the slot {a_[:, 1].mean() * 1e3:.0f} us (max {a_[:, 1].max() * 1e3:.0f}), encode {a_[:, 2].mean():.3f} ms", file=sys.stderr, flush=True)
-    # the pipelined steps (encode of batch i next to the decodes of batches i-1, i-2) must reproduce the solo pass bit for bit
-    lp_, ll_ = state["last_local"][0][:B0], state["last_local"][1][:B0]
-    kp_all, kl_all = state["keep"]
-    state["keep"] = None
-    kp, kl = kp_all[:, :B0], kl_all[:, :B0]      # batch 0 (the only one of the fixed workload) of every timed step against the solo pass
-    wp = min(kp.shape[2], lp_.shape[1])  # timed steps whose captions / scores of batch 0 differ from the solo pass
-    rot = torch.arange(kp.shape[0], device=dev) % NB   # step i encoded batch i % NB of the rotation
-    bad_steps = int(((kp[:, :, :wp] != solo_rot_p[rot][:, :B0, :wp]).flatten(1).any(dim=1) | (kl != solo_rot_l[rot][:, :B0]).flatten(1).any(dim=1)).sum().item()) if kp.shape[0] else 0
-    solo_preds, solo_lps = solo_rot_p[(n_timed - 1) % NB], solo_rot_l[(n_timed - 1) % NB]   # the last timed step's batch
+    # --dump-outputs: what the timed path returned in its last step -- ids (0-padded to max_pred) and scores of every clip
+    # (all-gathered on N > 1), on one GPU also the tag probabilities of the step's encode
+    if args.dump_outputs and rank == 0:
+        if gathered is not None:
+            dump = {"preds": gathered[0][-1], "lprobs": gathered[1][-1]}
+        else:
+            dump = {"preds": state["last_local"][0], "lprobs": state["last_local"][1], "clip_probs": torch.cat(state["last_clips"])}
+        dump_outputs(args.dump_outputs, {k: v.float().cpu().numpy() for k, v in dump.items()})
     # what the job returns: the (all-gathered) ids of the last timed step, every clip, in clip order.  Its hash lets a sharded run be
     # compared with the single-GPU run of the same clips (tests/test_gpu_bench_n2.py); on N > 1 every rank must hold the same table.
     import hashlib
     final_ids = gathered[0][-1] if gathered is not None else state["last_local"][0]
     final_ids = trim_captions(final_ids.cpu()) if final_ids.numel() else final_ids.cpu()
     captions_sha = hashlib.sha256(final_ids.to(torch.int32).contiguous().numpy().tobytes()).hexdigest()
-    gather_consistent = None
-    if world > 1:   # my rows of the gathered table (last window) are what I decoded, scores included; and every rank holds the same table
-        first = (n_rep - 1) * args.steps
-        ok_g = bool(torch.equal(gathered[0][:, clip0: clip0 + B], kp_all[first: first + args.steps]) and
-                    torch.equal(gathered[1][:, clip0: clip0 + B], kl_all[first: first + args.steps]))
-        dig = torch.tensor(list(bytes.fromhex(captions_sha)), dtype=torch.int32, device=cdev)
-        lo_d, hi_d = dig.clone(), dig.clone()
-        dist.all_reduce(lo_d, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hi_d, op=dist.ReduceOp.MAX)
-        flag_g = torch.tensor([1 if (ok_g and torch.equal(lo_d, hi_d)) else 0], dtype=torch.int32, device=cdev)
-        dist.all_reduce(flag_g, op=dist.ReduceOp.MIN)
-        gather_consistent = bool(flag_g.item())
-        if not gather_consistent:
-            raise SystemExit("bench: the all-gathered caption table differs between ranks or from a rank's own results")
-    pipeline_consistent = bool(bad_steps == 0 and torch.equal(lp_[:, : solo_preds.shape[1]], solo_preds[: lp_.shape[0], : lp_.shape[1]]) and
-                               torch.equal(ll_, solo_lps[: ll_.shape[0]]))
-    if not pipeline_consistent:
-        a_, b_ = lp_[:, : solo_preds.shape[1]], solo_preds[: lp_.shape[0], : lp_.shape[1]]
-        rows = (a_ != b_).any(dim=1).nonzero().flatten().tolist()
-        print(f"[bench] rank {rank}: {bad_steps} of {n_timed} pipelined steps returned other captions / scores than the un-pipelined pass of the same batch; last step: rows",
-              rows[:16], "of", a_.shape[0], "| score diffs:", int((ll_ != solo_lps[: ll_.shape[0]]).sum()), file=sys.stderr, flush=True)
-    if world > 1:  # every rank must agree before a number is printed
-        flag = torch.tensor([1 if pipeline_consistent else 0], dtype=torch.int32, device=cdev)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        pipeline_consistent = bool(flag.item())
-    if not pipeline_consistent and os.environ.get("CN_BENCH_STRICT", "1") != "0":
-        raise SystemExit("bench: pipelined and un-pipelined results differ (CN_BENCH_STRICT=0 reports the number anyway, with pipeline_consistent false)")
-    state["prof"] = None
-    prof = eng.profile_read()
-    eng.profile_enable(())
+    pipeline_consistent = gather_consistent = prof = None
+    if args.full:
+        # the pipelined steps (encode of batch i next to the decodes of batches i-1, i-2) must reproduce the solo pass bit for bit
+        lp_, ll_ = state["last_local"][0][:B0], state["last_local"][1][:B0]
+        kp_all, kl_all = state["keep"]
+        state["keep"] = None
+        kp, kl = kp_all[:, :B0], kl_all[:, :B0]      # batch 0 (the only one of the fixed workload) of every timed step against the solo pass
+        wp = min(kp.shape[2], lp_.shape[1])  # timed steps whose captions / scores of batch 0 differ from the solo pass
+        rot = torch.arange(kp.shape[0], device=dev) % NB   # step i encoded batch i % NB of the rotation
+        bad_steps = int(((kp[:, :, :wp] != solo_rot_p[rot][:, :B0, :wp]).flatten(1).any(dim=1) | (kl != solo_rot_l[rot][:, :B0]).flatten(1).any(dim=1)).sum().item()) if kp.shape[0] else 0
+        solo_preds, solo_lps = solo_rot_p[(n_timed - 1) % NB], solo_rot_l[(n_timed - 1) % NB]   # the last timed step's batch
+        if world > 1:   # my rows of the gathered table (last window) are what I decoded, scores included; and every rank holds the same table
+            first = (n_rep - 1) * args.steps
+            ok_g = bool(torch.equal(gathered[0][:, clip0: clip0 + B], kp_all[first: first + args.steps]) and
+                        torch.equal(gathered[1][:, clip0: clip0 + B], kl_all[first: first + args.steps]))
+            dig = torch.tensor(list(bytes.fromhex(captions_sha)), dtype=torch.int32, device=cdev)
+            lo_d, hi_d = dig.clone(), dig.clone()
+            dist.all_reduce(lo_d, op=dist.ReduceOp.MIN)
+            dist.all_reduce(hi_d, op=dist.ReduceOp.MAX)
+            flag_g = torch.tensor([1 if (ok_g and torch.equal(lo_d, hi_d)) else 0], dtype=torch.int32, device=cdev)
+            dist.all_reduce(flag_g, op=dist.ReduceOp.MIN)
+            gather_consistent = bool(flag_g.item())
+            if not gather_consistent:
+                raise SystemExit("bench: the all-gathered caption table differs between ranks or from a rank's own results")
+        pipeline_consistent = bool(bad_steps == 0 and torch.equal(lp_[:, : solo_preds.shape[1]], solo_preds[: lp_.shape[0], : lp_.shape[1]]) and
+                                   torch.equal(ll_, solo_lps[: ll_.shape[0]]))
+        if not pipeline_consistent:
+            a_, b_ = lp_[:, : solo_preds.shape[1]], solo_preds[: lp_.shape[0], : lp_.shape[1]]
+            rows = (a_ != b_).any(dim=1).nonzero().flatten().tolist()
+            print(f"[bench] rank {rank}: {bad_steps} of {n_timed} pipelined steps returned other captions / scores than the un-pipelined pass of the same batch; last step: rows",
+                  rows[:16], "of", a_.shape[0], "| score diffs:", int((ll_ != solo_lps[: ll_.shape[0]]).sum()), file=sys.stderr, flush=True)
+        if world > 1:  # every rank must agree before a number is printed
+            flag = torch.tensor([1 if pipeline_consistent else 0], dtype=torch.int32, device=cdev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            pipeline_consistent = bool(flag.item())
+        if not pipeline_consistent and os.environ.get("CN_BENCH_STRICT", "1") != "0":
+            raise SystemExit("bench: pipelined and un-pipelined results differ (CN_BENCH_STRICT=0 reports the number anyway, with pipeline_consistent false)")
+        state["prof"] = None
+        prof = eng.profile_read()
+        eng.profile_enable(())
     rank_rates = None
     if world > 1:  # a window's time is the slowest rank's; per-rank rates show an imbalance between the GPUs
         mine = torch.tensor(win_dt + own_dt + [float(B), audio_seconds], dtype=torch.float64, device=cdev)
@@ -1019,36 +1070,38 @@ def main() -> None:
         rr = (rank_tab[:, 2 * n_rep] * args.steps / rank_tab[:, n_rep + med]).tolist()
         rank_rates = {"min": round(min(rr), 2), "max": round(max(rr), 2), "per_rank": [round(v, 2) for v in rr]}
 
-    dom_ms, dom_n = prof[dominant]
-    n_prof_steps = sum(1 for i_ in range(n_timed) if i_ % prof_every == 0)
-    launches_per_step = dom_n / n_prof_steps
-    avg_launch_s = dom_ms * 1e-3 / dom_n
-    roof = {"kernel": dominant, "avg_launch_us": round(avg_launch_s * 1e6, 2), "launches_per_step": launches_per_step,
-            "launches_timed": dom_n, "timed_steps_with_events": n_prof_steps,
-            "traffic": None}
-    if args.workload == "fixed":
-        fl, by = algorithmic_work(dominant, B, 2.0 if args.precision in ("bf16", "f16", "bf16+f16dec", "mixed", "mixed16") else 4.0)
-        if dominant in ("pw1_gemm", "pw2_gemm"):
-            achieved = fl / launches_per_step / avg_launch_s / 1e12
-            roof.update({"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_BF16_TFLOPS, 4)})
-        else:
-            achieved = by / launches_per_step / avg_launch_s / 1e9
-            roof.update({"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                         "frac": round(achieved / PEAK_HBM_GBS, 4)})
-        if args.precision == "bf16":
-            tr, src = pmc_traffic(dominant, B, launches_per_step)
-            if tr is not None:
-                roof["traffic"] = round(tr)            # HBM bytes per launch (class average), PMC
-                roof["traffic_unit"] = "bytes/launch"
-                roof["traffic_source"] = "profiles/" + src
-                roof["traffic_measured_on_this_build"] = pmc_is_current(os.path.join(ROOT, "profiles", src))
-                roof["algorithmic_bytes_per_launch"] = round(by / launches_per_step)
-            mb, src = pmc_mfma_busy(dominant)
-            if mb is not None:
-                roof["mfma_busy"] = mb                 # share of SIMD cycles with the matrix pipe busy, PMC
-                roof["mfma_busy_source"] = "profiles/" + src
-                roof["mfma_busy_measured_on_this_build"] = pmc_is_current(os.path.join(ROOT, "profiles", src))
+    roof = None
+    if args.full:
+        dom_ms, dom_n = prof[dominant]
+        n_prof_steps = sum(1 for i_ in range(n_timed) if i_ % prof_every == 0)
+        launches_per_step = dom_n / n_prof_steps
+        avg_launch_s = dom_ms * 1e-3 / dom_n
+        roof = {"kernel": dominant, "avg_launch_us": round(avg_launch_s * 1e6, 2), "launches_per_step": launches_per_step,
+                "launches_timed": dom_n, "timed_steps_with_events": n_prof_steps,
+                "traffic": None}
+        if args.workload == "fixed":
+            fl, by = algorithmic_work(dominant, B, 2.0 if args.precision in ("bf16", "f16", "bf16+f16dec", "mixed", "mixed16") else 4.0)
+            if dominant in ("pw1_gemm", "pw2_gemm"):
+                achieved = fl / launches_per_step / avg_launch_s / 1e12
+                roof.update({"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_BF16_TFLOPS, 4)})
+            else:
+                achieved = by / launches_per_step / avg_launch_s / 1e9
+                roof.update({"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                             "frac": round(achieved / PEAK_HBM_GBS, 4)})
+            if args.precision == "bf16":
+                tr, src = pmc_traffic(dominant, B, launches_per_step)
+                if tr is not None:
+                    roof["traffic"] = round(tr)            # HBM bytes per launch (class average), PMC
+                    roof["traffic_unit"] = "bytes/launch"
+                    roof["traffic_source"] = "profiles/" + src
+                    roof["traffic_measured_on_this_build"] = pmc_is_current(os.path.join(ROOT, "profiles", src))
+                    roof["algorithmic_bytes_per_launch"] = round(by / launches_per_step)
+                mb, src = pmc_mfma_busy(dominant)
+                if mb is not None:
+                    roof["mfma_busy"] = mb                 # share of SIMD cycles with the matrix pipe busy, PMC
+                    roof["mfma_busy_source"] = "profiles/" + src
+                    roof["mfma_busy_measured_on_this_build"] = pmc_is_current(os.path.join(ROOT, "profiles", src))
 
     result = None
     if rank == 0:
@@ -1061,13 +1114,9 @@ def main() -> None:
                   f"(min 3 / max 20 tokens, V=5631), synthetic seeded checkpoint")
         result = {
             "metric": "clips_per_sec", "value": round(clips_per_s, 2), "unit": "clips/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "warmup_run": warm_used, "ms_per_step": round(dt / args.steps * 1e3, 3), "pipeline_consistent": pipeline_consistent, "pipeline_steps_checked": n_keep if n_keep else 1,
-            "captions_sha256": captions_sha, "gather": ({"collectives_per_window": 2, "consistent_across_ranks": gather_consistent,
-                                                        "what": "ids (K, B, max_pred) int32 + scores (K, B) fp32 of all K steps of a window, once per window"} if world > 1 else None),
-            "timed_region_s": round(dt, 4), "repeat": n_rep, "repeat_requested": args.repeat, "min_timed_total_s": min_timed_s,
+            "steps": args.steps, "warmup": args.warmup, "warmup_run": warm_used, "ms_per_step": round(dt / args.steps * 1e3, 3), "full": args.full,
+            "captions_sha256": captions_sha, "timed_region_s": round(dt, 4), "repeat": n_rep,
             "host_enqueue_ms_per_step": round(issue_dt[med] / args.steps * 1e3, 3),   # host time to enqueue a step (median window): below ms_per_step = the device, not the host, bounds the step
-            "windows": {"clips_per_sec": [round(total_clips * args.steps / w, 2) for w in win_dt], "median_index": med,
-                        "spread": round((max(win_dt) - min(win_dt)) / dt, 4), "timed_total_s": round(sum(win_dt), 4)},
             "rank_clips_per_sec": rank_rates,
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": {"bf16": "bf16", "fp32": "f32", "exact": "f16x2", "mixed": "bf16 encoder + f16x2 decoder", "f16": "f16",
@@ -1078,6 +1127,16 @@ def main() -> None:
                        "decode_group": G, "decode_streams": n_decg if G > 1 else n_dec, "encode_streams": len(s_encs), "input_batches_rotated": NB,
                        **({"share_gpu_selftest": True} if share else {})},
             "audio_seconds_per_sec": round(audio_seconds_all * args.steps / dt, 1),
+            "decode_schedule": schedule,
+        }
+    if rank == 0 and args.full:
+        result.update({
+            "pipeline_consistent": pipeline_consistent, "pipeline_steps_checked": n_keep if n_keep else 1,
+            "gather": ({"collectives_per_window": 2, "consistent_across_ranks": gather_consistent,
+                        "what": "ids (K, B, max_pred) int32 + scores (K, B) fp32 of all K steps of a window, once per window"} if world > 1 else None),
+            "repeat_requested": args.repeat, "min_timed_total_s": min_timed_s,
+            "windows": {"clips_per_sec": [round(total_clips * args.steps / w, 2) for w in win_dt], "median_index": med,
+                        "spread": round((max(win_dt) - min(win_dt)) / dt, 4), "timed_total_s": round(sum(win_dt), 4)},
             "decode_tokens_per_sec": round(world * best_tokens / (decode_ms * 1e-3), 1),   # solo decode (pre-pass)
             "decode_tokens_per_sec_pipelined": round(total_clips / B0 * best_tokens * args.steps / dt, 1) if args.workload == "fixed" else None,
             "decode_beam_row_steps_per_sec": round(world * beam_tokens / (decode_ms * 1e-3), 1),
@@ -1085,8 +1144,7 @@ def main() -> None:
             "decode_grouped": ({"batches_per_search": G, "search_ms": round(decode_ms_grouped, 3), "ms_per_batch": round(decode_ms_grouped / G, 3),
                                 "launches_per_batch_step": round(graph_nodes_grouped / max_pred / G, 2)} if G > 1 else None),
             "roofline": roof,
-            "decode_schedule": schedule,
-        }
+        })
         if args.workload == "fixed":
             n_steps = int(out["sizes"][0].item())
             dby = decode_algorithmic_bytes(B0, beam, t0_, n_steps, eng.vocab_size)
@@ -1105,7 +1163,7 @@ def main() -> None:
 
     # ---- CPU baseline (rank 0, N = 1 only): the oracle restatement on host cores; its outputs are KEPT as the checker ----
     ora = None
-    if rank == 0 and world == 1 and args.cpu_clips > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_clips > 0:
         from oracle import cpu_ref as O
 
         n_thr = max(1, min(args.cpu_threads, len(os.sched_getaffinity(0))))
@@ -1135,9 +1193,9 @@ def main() -> None:
                        "frame_embs": ofe}
 
     # ---- parity of every precision against the ORACLE + attribution of the bf16 disagreement (rank 0, N = 1, untimed) ----
-    if rank == 0 and world == 1 and args.parity_clips > 0 and args.workload == "fixed":
+    if args.full and rank == 0 and world == 1 and args.parity_clips > 0 and args.workload == "fixed":
         result["parity"] = parity_report(args, Engine, eng, sd, dev, w0, lens0, bos0, forbid, t0_, beam, min_pred, max_pred, ora, result)
-    if rank == 0 and world == 1 and args.workload == "fixed" and args.precision == "bf16" and args.also and args.parity_clips > 0:
+    if args.full and rank == 0 and world == 1 and args.workload == "fixed" and args.precision == "bf16" and args.also and args.parity_clips > 0:
         result["also_pipelined"] = also_pipelined(args, B0)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -116,21 +116,14 @@ REFERENCE_DEFAULTS = {"proj_name": "lin768", "min_pred_size": 3, "max_pred_size"
 
 def test_constructor_defaults_are_the_references():
     """a BaselinePLM built without decode hyper-parameters must search like the reference's (beam_size 10, not 2)."""
-    import ast
     import inspect
     from conette_amd.baseline import BaselinePLM
     sig = inspect.signature(BaselinePLM.__init__)
     ours = {k: sig.parameters[k].default for k in REFERENCE_DEFAULTS}
     assert ours == REFERENCE_DEFAULTS
-    ref_file = "/root/reference/src/conette/pl_modules/baseline.py"
-    if os.path.isfile(ref_file):      # (this container only: the golden list above against the reference's own source)
-        tree = ast.parse(open(ref_file).read())
-        init = next(f for c in tree.body if isinstance(c, ast.ClassDef) and c.name == "BaselinePLM"
-                    for f in c.body if isinstance(f, ast.FunctionDef) and f.name == "__init__")
-        names = [a.arg for a in init.args.args][1:]
-        vals = [ast.literal_eval(d) for d in init.args.defaults]
-        ref = dict(zip(names[len(names) - len(vals):], vals))
-        assert {k: ref[k] for k in REFERENCE_DEFAULTS} == REFERENCE_DEFAULTS
+    # the golden list above against the reference's own BaselinePLM.__init__ defaults, recorded from its source
+    ref = json.load(open(os.path.join(G.GOLDEN, "baseline", "reference_init_defaults.json")))
+    assert {k: ref[k] for k in REFERENCE_DEFAULTS} == REFERENCE_DEFAULTS
 
 
 @pytest.mark.gpu

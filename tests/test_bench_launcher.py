@@ -118,3 +118,27 @@ def test_decode_group_choice():
         for b in (1, 11, 16, 64, 100, 256, 1000):
             g = bench.choose_decode_group(steps, b, 3)
             assert steps % g == 0 and (g == 1 or g * b <= 256) and g * b * 3 < 4096 or g == 1
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 <name>.npy per array; above the size limit, the same seeded sample of clips from every array."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    preds = np.arange(40 * 20, dtype=np.int32).reshape(40, 20) % 5631
+    lp = -np.linspace(0.5, 9.0, 40).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"preds": preds, "lprobs": lp})
+    got = np.load(tmp_path / "a" / "preds.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, preds.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "lprobs.npy"), lp)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["lprobs.npy", "preds.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)   # 84 bytes per clip: a sample of 11 of the 40 clips
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"preds": preds, "lprobs": lp})
+    rows = np.load(tmp_path / "b" / "rows.npy").astype(np.int64)
+    sub = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in ("preds", "lprobs", "rows")}
+    assert sum(a.nbytes for a in sub.values()) <= 1000 and len(rows) == 11 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(sub["preds"], preds[rows].astype(np.float32)) and np.array_equal(sub["lprobs"], lp[rows])
+    for n in ("preds", "lprobs", "rows"):
+        assert np.array_equal(np.load(tmp_path / "c" / (n + ".npy")), sub[n])

@@ -153,14 +153,17 @@ def test_wav_reader_formats(tmp_path):
                 load_audio(p)
 
 
-def test_unsupported_architecture_config_is_refused():
+def test_unsupported_architecture_config_is_refused(synth_weights, synth_cfg):
     import pytest
     import conette_amd  # noqa: F401
     from conette_amd import CoNeTTEConfig
     from conette_amd.model import CoNeTTEModel
     for kw in ({"acti_name": "relu"}, {"proj_name": "lin512"}):
         with pytest.raises((ValueError, RuntimeError)) as e:
-            CoNeTTEModel(CoNeTTEConfig(**kw), state_dict={})
+            # (a complete synthetic checkpoint and a tag mapping: with a GPU present, construction gets as far as the architecture
+            # check instead of stopping at the missing tokenizer or the AudioSet CSV that is not on disk)
+            CoNeTTEModel(CoNeTTEConfig(**{**synth_cfg, **kw}), state_dict=dict(synth_weights), offline=True,
+                         audioset_idx_to_name={i: f"tag{i}" for i in range(527)})
         assert "Unsupported config" in str(e.value) or "GPU" in str(e.value) or "missing" in str(e.value).lower()
 
 

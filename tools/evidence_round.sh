@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd $ROOT
-run() { name=$1; shift; timeout 600 python3 bench.py "$@" 2> $OUT/${TAG}_${name}.err | tail -1 > $OUT/${TAG}_${name}.json; python3 -c "
+run() { name=$1; shift; timeout 600 python3 bench.py --full "$@" 2> $OUT/${TAG}_${name}.err | tail -1 > $OUT/${TAG}_${name}.json; python3 -c "
 import json,sys
 d=json.load(open('$OUT/${TAG}_${name}.json'))
 print('$name', d['value'], d['unit'], 'ms/step', d['ms_per_step'], 'windows', d['windows']['clips_per_sec'], 'consistent', d['pipeline_consistent'])"; }

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out; mkdir -p $OUT
 TAG=${1:-pipe_gaps}
 cd /tmp && export TMPDIR=/tmp
 export CN_SCHED_TRIAL=0
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/${TAG}_trace -o run -- python3 $ROOT/bench.py --steps 24 --warmup 8 --cpu-clips 0 --parity-clips 0 "${@:2}" > $OUT/${TAG}.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/${TAG}_trace -o run -- python3 $ROOT/bench.py --full --steps 24 --warmup 8 --cpu-clips 0 --parity-clips 0 "${@:2}" > $OUT/${TAG}.log 2>&1
 tail -1 $OUT/${TAG}.log | cut -c1-200
 python3 - <<PY | tee $OUT/${TAG}.txt
 import csv, glob, collections

@@ -11,7 +11,7 @@ cd $ROOT
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 NGPU=$(python3 -c "import torch; print(torch.cuda.device_count())")
 echo "[scale_round] $NGPU GPUs visible"
-line() { name=$1; shift; timeout 1200 python3 bench.py "$@" --cpu-clips 0 --parity-clips 0 --also "" 2> $OUT/${TAG}_scale_${name}.err | tail -1 > $OUT/${TAG}_scale_${name}.json; }
+line() { name=$1; shift; timeout 1200 python3 bench.py --full "$@" --cpu-clips 0 --parity-clips 0 --also "" 2> $OUT/${TAG}_scale_${name}.err | tail -1 > $OUT/${TAG}_scale_${name}.json; }
 for n in 1 2 4 8; do
   if [ $n -le $NGPU ]; then line n$n --gpus $n --steps 100 --warmup 5; fi
 done
