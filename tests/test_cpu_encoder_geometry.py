@@ -1,0 +1,128 @@
+"""CPU: the tile rules that tests/encoder_geometry.py mirrors equal the ones in the kernel sources, and its table of encode cases
+reaches every depthwise tail, fused-MLP tail and cn_gemm2 regime at 256 compute units.  A retuned tile fails here until the
+table (and the cases that reach its tails) is revisited."""
+import os
+import re
+
+import pytest
+
+from tests import encoder_geometry as E
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "conette-audio-captioning_amd", "csrc")
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _one(pattern, text):
+    found = set(re.findall(pattern, text))
+    assert len(found) == 1, (pattern, found)
+    return int(found.pop())
+
+
+def test_depthwise_tiles_match_the_sources():
+    enc = _src("encoder.hip")
+    assert _one(r"#define CN_DW96_TH (\d+)", enc) == E.CN_DW96_TH
+    assert _one(r"#define CN_DW192_TH (\d+)", enc) == E.CN_DW192_TH
+    assert _one(r"#define CN_FW_TH (\d+)", enc) == E.CN_FW_TH
+    assert _one(r"launch_dwconv_fw<T, XT, 768, 7, (\d+)>", enc) == E.FW768_TH
+    # the fp32 stream's rows per tile at stages 0 / 1 (dwconv_dispatch: "(sizeof(XT) == 2 && CN_DW_DOT2) ? CN_DW96_TH : 8")
+    assert _one(r"\? CN_DW96_TH : (\d+)>", enc) == E.F32_DW_TH
+    assert _one(r"\? CN_DW192_TH : (\d+)>", enc) == E.F32_DW_TH
+    # stage 2 / 3 run the full-width kernels only at the widths of the encoder's geometry
+    assert "if (W == 14) return launch_dwconv_fw<T, XT, 384, 14, CN_FW_TH" in enc and E.WIDTHS[2] == 14
+    assert "if (W == 7) return launch_dwconv_fw<T, XT, 768, 7," in enc and E.WIDTHS[3] == 7
+
+
+def test_fused_mlp_tiles_match_the_sources():
+    for name in ("mlp_rc2.h", "mlp_sp.h"):
+        src = _src(name)
+        shifts = re.findall(r"n_tiles = \(M \+ 31\) >> (\d+);", src)
+        assert shifts and {int(s) for s in shifts} == {5}, (name, shifts)
+    for name in ("mlp_rc2.h", "mlp_sp.h", "mlp_rs16.h"):
+        assert re.findall(r"cn_rc2_grid\(\(M \+ 31\) / (\d+),", _src(name)) and \
+            {int(v) for v in re.findall(r"cn_rc2_grid\(\(M \+ 31\) / (\d+),", _src(name))} == {E.MLP_TILE}, name
+    assert 1 << 5 == E.MLP_TILE
+
+
+def test_gemm2_dispatch_matches_the_sources():
+    g2 = _src("gemm2.h")
+    assert {int(v) for v in re.findall(r"if \(M >= (\d+)\) \{", g2)} == {E.G2_M128}
+    assert _one(r"N % 256 == 0 && M >= (\d+) && splits == 1", g2) == E.G2_M256
+    body = g2[g2.index("static int cn_gemm2(const bf16_t* A"):g2.index("static int cn_gemm2(const half_t* A")]
+    tiles = {tuple(int(v) for v in t) for t in re.findall(r"cn_launch_gemm2_t<(\d+), (\d+), (\d+), (\d+),", body)}
+    assert tiles == {(128, 128, 32, 2), (128, 96, 64, 2), (224, 192, 64, 3), (224, 256, 64, 2), (256, 256, 64, 2),
+                     (128, 128, 64, 2), (64, 64, 32, 2), (64, 64, 64, 2)}, tiles
+    # the comments of the rule state two of its outcomes at 256 CUs (M = 13 888: the benchmark's stage 3)
+    assert E.gemm2_regime(13888, 3072, 768, 256) == "224x256"
+    assert E.gemm2_regime(13888, 768, 3072, 256) == "224x192ring" and E.gemm2_regime(13888, 768, 1536, 256) == "224x192ring"
+    # the exact precision's products: 128 x 96 when N is a multiple of 96 but not of 128
+    sp = g2[g2.index("static int cn_gemm2_sp("):g2.index("// type-generic front end")]
+    assert "if (n96) return cn_launch_gemm2_t<128, 96, 64, 2" in sp and "return cn_launch_gemm2_t<64, 64, 64, 2" in sp
+
+
+def test_encode_dispatch_matches_the_products():
+    """The products tests/encoder_geometry.products() lists are the ones encode_impl sends to cn_mm: the 16-bit precisions fuse
+    the MLPs of stages 0-2 (C <= 384) and the downsamples into stages 1-2 (Cp <= 192), the exact precision fuses stages 0-1."""
+    enc = _src("encoder.hip")
+    assert "if (bw.mlp_stream != nullptr && C <= 384)" in enc
+    assert "if (bw.mlp_sp != nullptr && C <= 192)" in enc
+    assert "if (Cp <= 192 && dw.fused != nullptr)" in enc
+    assert "if (i <= 1 && ctx->esize == 2)" in _src("api.hip")
+
+
+@pytest.mark.parametrize("n", [7680, 8000, 8319, 8320, 15040, 33000, 160000, 319999, 320000, 480000])
+def test_geometry_equals_the_engines(n):
+    from conette_amd.engine import encoder_geometry
+    assert E.geometry(n) == encoder_geometry(n)
+    for c in E.cases(256):
+        assert E.geometry(c.n_samples) == encoder_geometry(c.n_samples)
+
+
+def test_cases_have_distinct_clips():
+    seeds = set()
+    for c in E.cases(256):
+        assert len(set(c.lengths)) == c.b and E.geometry(c.n_samples)[1][3] >= 1, c.name
+        s = set(range(c.seed0, c.seed0 + c.b))
+        assert not (s & seeds), c.name
+        seeds |= s
+    assert all(1 <= c.b <= 6 for c in E.small_cases())
+
+
+def test_coverage_is_complete_at_256_cus():
+    cov = E.coverage(E.cases(256), 256)
+    want = E.reachable(256)
+    assert want - cov == set(), sorted(want - cov, key=str)
+    # every depthwise residue at every stage, both streams
+    for stream in ("f16", "f32"):
+        for st in range(4):
+            assert {r for (k, r) in cov if k == f"dw_{stream}_s{st}"} == set(range(E.DW_TH[stream][st])), (stream, st)
+    # maps no taller than the halo: H3 = 1 .. 7 (stage 3 at 7 rows is 2 tiles) and H2 <= 6
+    assert {h for (k, h) in cov if k == "dw_s3_narrow"} == set(range(1, 7))
+    assert {h for (k, h) in cov if k == "dw_s2_narrow"} == set(range(2, 7))
+    # every reachable M mod 32 of the fused MLPs
+    for st, step in enumerate((8, 4, 2)):
+        assert {r for (k, r) in cov if k == f"mlp_s{st}"} == set(range(0, 32, step)), st
+    # every cn_gemm2 regime of the stage-3 products (up to the benchmark's batch), every cn_gemm2_sp regime of the exact ones
+    regs = lambda key: {r for (k, r) in cov if k == key}
+    assert regs("bf16:pw1_s3") == {"64x64", "128x128", "256x256", "224x256"}
+    assert regs("bf16:pw2_s3") == regs("bf16:down3") == {"64x64", "128x128", "224x192ring"}
+    for p in ("pw1_s2", "pw2_s2", "pw1_s3", "pw2_s3", "down2", "down3"):
+        assert regs("exact:" + p) == {"64x64", "128x128"}, p
+    assert regs("exact:down1") == {"64x64", "128x96"}
+
+
+def test_large_batches_follow_the_rule():
+    lb = E.large_batches(256)
+    assert lb == {"128": 19, "256": 44, "bench": E.BENCH_BATCH}
+    for n_cu in (256, 304):
+        b = E.large_batches(n_cu)["256"]
+        assert E.gemm2_regime(b * 217, 3072, 768, n_cu) == "256x256" != E.gemm2_regime((b - 1) * 217, 3072, 768, n_cu)
+
+
+def test_tail_helpers():
+    assert list(E.dw_tail_rows("f16", 0, 252)) == [] and list(E.dw_tail_rows("f16", 0, 253)) == [252]
+    assert list(E.dw_tail_rows("f32", 0, 21)) == list(range(16, 21))
+    assert list(E.mlp_tail_positions(64)) == list(range(32, 64)) and list(E.mlp_tail_positions(65)) == [64]

@@ -22,12 +22,9 @@ import pytest
 import torch
 
 from tests import golden_util as G
+from tests.block_oracle import FP32_BOUND, ROUNDING, _assert_close, _nchw
 
 pytestmark = pytest.mark.gpu
-
-
-# operand rounding relative to bf16: every tolerance below that is made of operand rounding is multiplied by this
-ROUNDING = {"bf16": 1.0, "f16": 0.125}
 
 
 @pytest.fixture(scope="module", params=["bf16", "f16"])
@@ -43,27 +40,6 @@ def _wave(g):
     from conette_amd import synth
     n = [int(v) for v in g["lengths"]]
     return torch.from_numpy(synth.synth_waveforms(len(n), max(n), int(g["seed0"]), lengths=n))
-
-
-def _nchw(t):
-    return t.permute(0, 3, 1, 2).contiguous().cpu()
-
-
-def _assert_close(got, ref, what, k=1.0):
-    """Full tensor: rtol 3e-3 + atol 2e-3 (times k = ROUNDING[precision]) for all but a 1e-5 share of the elements (a hidden
-    value that rounds to the neighbouring bf16 moves an output by ~1e-3), nothing beyond 4x that bound, mean error far
-    inside it (fp16: + 2e-5 for the GELU polynomial's 2.5e-5, which no longer disappears under the operand rounding).
-    Round 5: both sides are stored to an fp16 residual stream (oracle: bf16_ref.res16), so a value may land on the fp16
-    neighbour of the oracle's -- one fp16 ulp (<= 2^-10 relative) on top of the bound; the MEAN bound does not move (a flip of
-    size ulp happens with probability |difference before rounding| / ulp)."""
-    err = (got - ref).abs()
-    bound = k * (2e-3 + 3e-3 * ref.abs()) + 2.0 ** -10 * ref.abs()
-    n_out = int((err > bound).sum())
-    assert n_out <= 1e-5 * err.numel(), (what, n_out, float(err.max()))
-    assert bool((err <= 4 * bound).all()), (what, float(err.max()))
-    # (round 5: 1.5e-4 where round 4 had 1e-4 -- the bf16 kernels' degree-3 GELU is 5.5e-5 off the erf form where the sigmoid
-    # form was 2.5e-5, so a few more hidden values land on the neighbouring bf16; measured worst block mean 1.0e-4)
-    assert float(err.mean()) < k * 1.5e-4 + (2e-5 if k < 1 else 0.0), (what, float(err.mean()))
 
 
 @pytest.mark.parametrize("name", ["b8_10s_beam3_all", "b3_mixed_beam3_none"])
@@ -94,12 +70,6 @@ def test_every_block_against_bf16_operand_oracle(name, eng_bf16, synth_weights):
             blk += 1
     assert torch.equal(taps["block17"], taps["stage3"]) and torch.equal(taps["block0"], taps["stage0_block0"])
     print("max / mean |err| per block:", {k: (round(a, 5), round(b, 7)) for k, (a, b) in worst.items()})
-
-
-# |block output - unmodified fp32 oracle's block output| on the GPU's own block input, measured in round 6 (worst of the 18 blocks,
-# b3_mixed fixture): bf16 max 0.0091 / mean 8.5e-4, f16 max 0.0024 / mean 2.4e-4 (the fp16 residual stream's store: half an fp16
-# ulp of an O(1) value, is in both); the bounds leave a factor ~2.
-FP32_BOUND = {"bf16": (0.02, 1.7e-3), "f16": (0.005, 5.0e-4)}
 
 
 def test_every_block_against_the_unmodified_fp32_oracle(eng_bf16, synth_weights):
