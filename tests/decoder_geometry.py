@@ -1,0 +1,359 @@
+"""Launch rules of the decoder and search kernels, mirrored from the sources, and the table of decoder geometries, searches and
+teacher-forcing cases that reaches every search-step instantiation, FFN regime, row tail and memory-length tail of them.
+
+tests/test_cpu_decoder_geometry.py holds the constants and rules here to the C++ sources (a retuned threshold fails there until
+this table is revisited), checks that ``GEOMETRIES`` covers every regime and that every search is decided by margins no
+operand rounding of the exact precisions can flip; tests/test_gpu_decoder_edges.py runs the cases.
+
+Sources mirrored (paths under conette-audio-captioning_amd/csrc):
+  * decoder.hip ``decode_impl``: the search step (``cn_search_step3_kernel<NR, VPT>`` for V <= S3_T * S3_VPT and beam <= 8, the
+    generic ``cn_search_step_kernel`` otherwise), the FFN path of a step (fused ``cn_dec_ffn_kernel`` with d_ff / 256 slabs, the
+    block kernel + two ``cn_gemm2`` launches, or one launch per sub-layer), the split-K of FFN2 and the rows per block.
+  * api.hip ``conette_create``: which geometries get the packed FFN stream (``d_ff % 256 == 0 && d_ff <= 2048``).
+  * gemm2.h ``cn_gemm2``: BK = 32 tiles when K is no multiple of 64.
+  * dec_block.h / dec_ffn.h / ctx.h: rows per block, keys per batch and batches in flight, rows per FFN tile, layer limit.
+
+No torch at import time: the helpers that build weights and inputs import it when called."""
+from __future__ import annotations
+
+from typing import Dict, List, NamedTuple, Optional, Set, Tuple
+
+S3_T = 1024                      # decoder.hip: #define S3_T 1024 (threads of the register-resident search step)
+S3_VPT = 8                       # decoder.hip: #define S3_VPT 8 (most logits per thread: V <= 8192)
+S3_MAX_BEAM = 8                  # decoder.hip: if (V <= S3_T * S3_VPT && beam <= 8)
+S3_KERNELS = ((4, 2), (4, 4), (4, 6), (4, 8), (8, 4), (8, 8))   # decoder.hip: the S3_LAUNCH(NR, VPT) instantiations
+CN_MAX_BEAM = 16                 # decoder.hip: #define CN_MAX_BEAM 16
+CN_MAX_PRED = 64                 # decoder.hip: #define CN_MAX_PRED 64
+FF2_SPLITS = 8                   # decoder.hip: #define FF2_SPLITS 8 (most slabs; split-K of the per-sub-layer FFN2)
+FF2_SPLITS_DEFAULT = 4           # decoder.hip: ff2_splits_default() (split-K of FFN2 behind the block kernel)
+FUSED_FFN_MAX = 2048             # api.hip: dff % 256 == 0 && dff <= 2048 (the packed stream of cn_dec_ffn_kernel)
+FFN_SLAB = 256                   # dec_ffn.h / decoder.hip: one slab per 256-wide hidden chunk
+DF_ROWS = 32                     # dec_ffn.h: #define DF_ROWS 32
+DB_ROWS = 4                      # dec_block.h: rows per block, 16-bit operands
+DB_ROWS_SP = 4                   # dec_block.h: rows per block, exact precision
+DB_WIDE_ROWS = 8                 # dec_block.h: rows per block of a wide search
+DB_WIDE_ROWS_SP = 8
+DB_WIDE_R = 512                  # dec_block.h: a search of R >= 512 rows is wide
+DB_NB_SELF = 8                   # dec_block.h: self-attention keys per batch
+DB_DEPTH_SELF = 2                # dec_block.h: batches in flight
+DB_NB_CROSS = 8                  # dec_block.h: cross-attention frames per batch
+DB_DEPTH_CROSS = 2
+ATTN_NB = 8                      # decoder.hip: constexpr int NB = 8 (keys per batch of the unfused attention kernels)
+CN_MAX_LAYERS = 12               # ctx.h: #define CN_MAX_LAYERS 12
+D_MODEL = 256
+N_SPECIALS_AND_TASKS = 11        # synth: 4 special tokens + 7 task tokens; V = n_words + 11
+
+PRECISIONS = ("fp32", "exact", "bf16", "f16")
+H16 = ("bf16", "f16")
+
+
+def ff2_splits_default() -> int:
+    return FF2_SPLITS_DEFAULT
+
+
+def _cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def vocab(n_words: int) -> int:
+    return n_words + N_SPECIALS_AND_TASKS
+
+
+def search_kernel(v: int, beam: int) -> Tuple:
+    """("s3", NR, VPT) or ("generic",): the search step decode_impl launches for a vocabulary of v entries at this beam."""
+    assert v >= 4 and 1 <= beam <= CN_MAX_BEAM
+    if v <= S3_T * S3_VPT and beam <= S3_MAX_BEAM:
+        vpt = _cdiv(v, S3_T)
+        if beam <= 4:
+            return ("s3", 4, 2 if vpt <= 2 else 4 if vpt <= 4 else 6 if vpt <= 6 else 8)
+        return ("s3", 8, 4 if vpt <= 4 else 8)
+    return ("generic",)
+
+
+def has_ffn_stream(d_ff: int) -> bool:
+    """conette_create packs the stream of the fused FFN kernel (16-bit and exact precisions)."""
+    return d_ff % FFN_SLAB == 0 and d_ff <= FUSED_FFN_MAX
+
+
+def ffn_regime(precision: str, d_ff: int, fusion: bool = True) -> str:
+    """The FFN path of a decode step.  ``fusion`` = False: conette_set_option(CONETTE_OPT_DECODE_FUSION, 0).
+    fused/<slabs>        cn_dec_ffn_kernel, d_ff / 256 slabs summed by the next block prologue / the final cn_ln256_kernel
+    block+gemm2/<splits> 16-bit, no packed stream: the block kernel, then cn_gemm2 (FFN1) and split-K cn_gemm2 (FFN2)
+    sublayer_sp/<splits> exact, one launch per sub-layer: cn_gemm2_sp, FFN2 split over <splits> slabs
+    sublayer_h16/<splits> 16-bit, one launch per sub-layer: cn_gemm2, FFN2 split over <splits> slabs
+    fp32                 gemm.h products, no slabs"""
+    assert d_ff % 32 == 0
+    if precision == "fp32":
+        return "fp32"
+    fused_ffn = has_ffn_stream(d_ff) and d_ff // FFN_SLAB <= FF2_SPLITS
+    if precision in H16:
+        if not fusion:
+            return "sublayer_h16/%d" % (FF2_SPLITS if d_ff % (FF2_SPLITS * 64) == 0 else 1)
+        if fused_ffn:
+            return "fused/%d" % (d_ff // FFN_SLAB)
+        s = ff2_splits_default()
+        if s < 1 or s > FF2_SPLITS or s > 8 or d_ff % (s * 64) != 0:
+            s = 1
+        return "block+gemm2/%d" % s
+    assert precision == "exact"
+    if fusion and fused_ffn:     # (the exact block kernel runs only together with the fused FFN)
+        return "fused/%d" % (d_ff // FFN_SLAB)
+    return "sublayer_sp/%d" % (FF2_SPLITS if d_ff % (FF2_SPLITS * 32) == 0 else 1)
+
+
+def ffn_regimes(precision: str, d_ff: int) -> Set[str]:
+    """both settings of the fusion option"""
+    return {ffn_regime(precision, d_ff, True), ffn_regime(precision, d_ff, False)}
+
+
+def k_tile(d_ff: int) -> int:
+    """BK of the cn_gemm2 tile of the FFN2 product (K = d_ff): 32 when K is no multiple of 64."""
+    return 64 if d_ff % 64 == 0 else 32
+
+
+def block_rows(precision: str, r: int) -> int:
+    """Rows per block of cn_dec_block_kernel."""
+    rows, wide = (DB_ROWS, DB_WIDE_ROWS) if precision in H16 else (DB_ROWS_SP, DB_WIDE_ROWS_SP)
+    return wide if (wide != rows and r >= DB_WIDE_R) else rows
+
+
+# ---- the case table ----------------------------------------------------------------------------------------------------------
+class Search(NamedTuple):
+    name: str
+    b: int
+    beam: int
+    ta: int
+    frame_lens: Tuple[int, ...]
+    min_pred: int
+    max_pred: int
+    seed: int
+
+    @property
+    def rows(self) -> int:
+        return self.b * self.beam
+
+
+class Forcing(NamedTuple):
+    name: str
+    b: int
+    ta: int
+    frame_lens: Tuple[int, ...]
+    cap_len: int
+    n_valid: Tuple[int, ...]     # pad layout: clip i holds n_valid[i] tokens (the task token first), then pad_id to cap_len
+    seed: int
+
+
+class Geometry(NamedTuple):
+    name: str
+    n_words: int
+    d_ff: int
+    n_layers: int
+    searches: Tuple[Search, ...]
+    forcing: Forcing
+
+    @property
+    def v(self) -> int:
+        return vocab(self.n_words)
+
+
+def _S(name, beam, ta, frame_lens, min_pred, max_pred, seed):
+    return Search(name, len(frame_lens), beam, ta, tuple(frame_lens), min_pred, max_pred, seed)
+
+
+def _F(name, ta, frame_lens, cap_len, n_valid, seed):
+    assert len(frame_lens) == len(n_valid)
+    return Forcing(name, len(frame_lens), ta, tuple(frame_lens), cap_len, tuple(n_valid), seed)
+
+
+# Seeds: the first of 0, 1, 2 ... at which the oracle's search meets the margin conditions of tests/test_cpu_decoder_geometry.py
+# (smallest effective margin of any call >= MIN_MARGIN, at least one clip with every call above F16_MARGIN).
+GEOMETRIES: Tuple[Geometry, ...] = (
+    # V = 31: 15 of the 16 waves of the s3 step hold no candidate, k * V as small as 31; d_ff = 32: one BK = 32 k-tile
+    Geometry("v31_ff32_l2", 20, 32, 2, (
+        _S("beam4_r1mod4", 4, 9, (9, 1, 7, 8, 5, 9, 2, 3), 3, 12, 0),            # R = 32
+        _S("beam8_r64", 8, 17, (16, 17, 9, 1, 7, 8, 12, 3), 3, 12, 2),           # R = 64
+        _S("beam16_generic", 16, 8, (8, 5, 3, 7), 2, 6, 13),                           # R = 32, CN_MAX_BEAM
+        _S("beam13_r65", 13, 7, (7, 3, 5, 1, 6), 2, 8, 1),                       # R = 65: one row in the third FFN tile
+    ), _F("cap1", 9, (9, 4, 1), 1, (1, 1, 1), 11)),
+    Geometry("v2048_ff96_l1", 2037, 96, 1, (
+        _S("beam1_r1", 1, 25, (25,), 3, 20, 0),                                  # R = 1
+        _S("beam5_r35", 5, 9, (9, 8, 7, 1, 5, 6, 3), 0, 12, 0),                  # R = 35, min_pred = 0
+    ), _F("ragged", 17, (17, 16, 9, 2), 10, (10, 6, 3, 1), 12)),
+    Geometry("v2049_ff256_l6", 2038, 256, 6, (
+        _S("beam4_r2mod4", 4, 16, (16, 9, 3), 3, 20, 1),                         # R = 12
+        _S("beam7_r63_short_mem", 7, 12, (8, 1, 7, 9, 2, 5, 6, 3, 4), 3, 10, 0),  # R = 63, every length below Ta
+        _S("beam2_maxpred64", 2, 8, (8, 7, 5), 60, 64, 0),                       # CN_MAX_PRED: bit 63 of kvalid, s_prefix[..][64]
+    ), _F("cap64_pad_mid", 9, (9, 7, 1), 64, (64, 37, 5), 13)),
+    Geometry("v4096_ff1024_l2", 4085, 1024, 2, (
+        _S("beam1_r3", 1, 32, (32, 25, 17), 3, 20, 0),                           # R = 3
+        _S("beam8_r8", 8, 9, (9,), 5, 14, 0),                                    # min_pred > 3
+        _S("beam11_r33_generic", 11, 8, (8, 7, 1), 3, 8, 3),                     # R = 33: one row in the second FFN tile
+    ), _F("ragged", 25, (25, 24, 8, 7, 1), 12, (12, 11, 7, 2, 1), 14)),
+    Geometry("v4097_ff1792_l1", 4086, 1792, 1, (
+        _S("beam4_never_finishes", 4, 7, (7, 6), 9, 9, 2),                       # min_pred = max_pred: nothing ends before the last step
+        _S("beam5_r5", 5, 17, (17,), 3, 20, 0),
+    ), _F("ragged", 16, (16, 15, 9), 9, (9, 4, 2), 15)),
+    # CN_MAX_LAYERS: kv_ld = 6144, the exact arena sized from d_ff
+    Geometry("v6144_ff2048_l12", 6133, 2048, 12, (
+        _S("beam1_r2", 1, 9, (9, 4), 3, 16, 0),
+        _S("beam8_r24", 8, 8, (8, 7, 4), 2, 6, 11),
+    ), _F("ragged", 10, (10, 9, 8, 3), 8, (8, 5, 3, 1), 16)),
+    Geometry("v6145_ff2080_l2", 6134, 2080, 2, (
+        _S("beam4_r36", 4, 9, (9, 8, 7, 6, 5, 4, 3, 2, 1), 3, 12, 0),            # R = 36
+        _S("beam5_r10", 5, 16, (16, 8), 3, 16, 1),
+    ), _F("ragged", 9, (9, 8, 1), 7, (7, 3, 2), 17)),
+    Geometry("v8192_ff2304_l6", 8181, 2304, 6, (
+        _S("beam1_r5", 1, 17, (17, 9, 8, 7, 1), 3, 20, 0),
+        _S("beam8_r24", 8, 9, (9, 5, 2), 3, 6, 43),
+        _S("beam9_generic", 9, 8, (8, 3, 7, 5), 3, 6, 3),                             # the boundary of the generic step
+    ), _F("ragged", 8, (8, 7, 2), 9, (9, 8, 1), 18)),
+    # V > 8192: the generic step at a beam the s3 step would take
+    Geometry("v8193_ff4096_l2", 8182, 4096, 2, (
+        _S("beam5_generic", 5, 9, (9, 8, 1), 3, 14, 0),
+        _S("beam3_generic", 3, 25, (25, 16), 3, 20, 0),
+    ), _F("ragged", 9, (9, 8, 7, 1), 11, (11, 10, 4, 1), 19)),
+)
+
+# geometries whose 16-bit forcing bound is measured, not inherited (deeper or wider than the 6 x 2048 decoder the inherited
+# bounds were measured at): tests/test_gpu_decoder_edges.py
+MEASURED_BOUND_GEOMETRIES = ("v6144_ff2048_l12", "v8193_ff4096_l2")
+
+MIN_MARGIN = 2e-3                # condition on the inputs: 4 x the 5e-4 tie tolerance of the exact precisions
+R16 = {"bf16": 1.0, "f16": 0.125}
+F16_MARGIN = 0.25 * R16["f16"]   # a clip whose every call is above this is decided identically by the f16 precision
+
+
+def geometry(name: str) -> Geometry:
+    return next(g for g in GEOMETRIES if g.name == name)
+
+
+def coverage(geoms=GEOMETRIES) -> Dict[str, set]:
+    """What the table reaches, by the mirrored rules."""
+    cov: Dict[str, set] = {k: set() for k in ("search", "search_v_beam", "beam", "ffn", "d_ff", "k_tile", "layers", "rows", "rows_mod4",
+                                              "mem_len", "max_pred", "min_pred", "cap_len", "block_rows")}
+    for g in geoms:
+        cov["d_ff"].add(g.d_ff)
+        cov["k_tile"].add(k_tile(g.d_ff))
+        cov["layers"].add(g.n_layers)
+        for p in PRECISIONS:
+            for fusion in (True, False):
+                cov["ffn"].add((p, ffn_regime(p, g.d_ff, fusion)))
+        for s in g.searches:
+            cov["search"].add(search_kernel(g.v, s.beam))
+            cov["search_v_beam"].add((g.v, s.beam, search_kernel(g.v, s.beam)))
+            cov["beam"].add(s.beam)
+            cov["rows"].add(s.rows)
+            cov["rows_mod4"].add(s.rows % 4)
+            cov["mem_len"] |= set(s.frame_lens)
+            cov["max_pred"].add(s.max_pred)
+            cov["min_pred"].add(s.min_pred)
+            for p in PRECISIONS:
+                cov["block_rows"].add((p, block_rows(p, s.rows)))
+        cov["cap_len"].add(g.forcing.cap_len)
+        cov["mem_len"] |= set(g.forcing.frame_lens)
+    return cov
+
+
+# ---- weights, inputs and oracle runs (torch imported on use) ---------------------------------------------------------------
+_WEIGHTS: Dict[str, dict] = {}
+
+
+def weights(g: Geometry) -> dict:
+    """The decoder-only state dict of a geometry (the ``model.*`` tensors of the peaked synthetic checkpoint), as torch tensors."""
+    if g.name not in _WEIGHTS:
+        from conette_amd import synth
+        from oracle import cpu_ref as O
+        sd = synth.synth_state_dict(n_words=g.n_words, d_ff=g.d_ff, n_layers=g.n_layers, recipe="peaked")
+        _WEIGHTS[g.name] = O.to_torch({k: v for k, v in sd.items() if k.startswith("model.")})
+    return _WEIGHTS[g.name]
+
+
+def drop_weights(g: Optional[Geometry] = None) -> None:
+    if g is None:
+        _WEIGHTS.clear()
+    else:
+        _WEIGHTS.pop(g.name, None)
+
+
+PAD_FRAME_SCALE = 8.0            # frames behind a clip's length hold larger values than any real frame: they must be ignored
+
+
+def frames(b: int, ta: int, frame_lens, seed: int):
+    """(frame_embs (B, Ta, 768) fp32, audio_shape (B, 2) int64): seeded frames at the scale of the encoder's (std 0.65)."""
+    import numpy as np
+    import torch
+    rng = np.random.Generator(np.random.PCG64(77000 + seed))
+    fe = ((rng.random((b, ta, 768)) * 2.0 - 1.0) * (0.65 * 3 ** 0.5)).astype(np.float32)
+    for i, n in enumerate(frame_lens):
+        assert 1 <= n <= ta
+        fe[i, n:] *= PAD_FRAME_SCALE
+    shape = torch.tensor([[768, n] for n in frame_lens], dtype=torch.int64)
+    return torch.from_numpy(fe), shape
+
+
+def search_inputs(g: Geometry, s: Search):
+    """(frame_embs, audio_shape, bos_ids (B,) int64, forbid mask (V,) bool) of a search: clip i is prompted with task (seed + i) % 7."""
+    import torch
+    w = weights(g)
+    fe, shape = frames(s.b, s.ta, s.frame_lens, s.seed)
+    tasks = torch.as_tensor([(s.seed + i) % 7 for i in range(s.b)])
+    return fe, shape, w["model.task_id_to_token_id"][tasks], w["model.forbid_rep_mask"].bool()
+
+
+def oracle_search(g: Geometry, s: Search) -> dict:
+    """oracle.cpu_ref.generate on the case, with its per-call trace flattened to (step, clip, parents, tokens, sums, margin)."""
+    import torch
+    from oracle import cpu_ref as O
+    w = weights(g)
+    fe, shape, bos, forbid = search_inputs(g, s)
+    with torch.no_grad():
+        mem, mask = O.encode_audio(w, fe, shape)
+        trace: list = []
+        best, best_lp, mult, mult_lp = O.generate(w, mem, mask, bos, vocab_size=g.v, beam_size=s.beam, min_pred_size=s.min_pred,
+                                                  max_pred_size=s.max_pred, forbid_rep_mask=forbid, n_layers=g.n_layers, trace=trace)
+    calls = [(step, c["clip"], c["parent"], c["token"], c["sum_lprob"], c["margin"]) for step, st in enumerate(trace) for c in st]
+    return {"best_preds": best, "best_lprobs": best_lp, "mult_preds": mult, "mult_lprobs": mult_lp, "calls": calls,
+            "mem": mem, "mask": mask}
+
+
+def effective_margin(call) -> float:
+    """Smallest gap among a call's top-(k+1) candidates: the recorded gap to the first rejected candidate and the gaps between
+    consecutive picks (their order decides the row slots)."""
+    _, _, par, _, sums, margin = call
+    return min([margin] + [sums[i] - sums[i + 1] for i in range(len(par) - 1)])
+
+
+def forcing_inputs(g: Geometry, f: Forcing):
+    """(frame_embs, audio_shape, caps_in (B, cap_len) int64): row i = task token, seeded word ids, then pad_id from n_valid[i] on."""
+    import numpy as np
+    import torch
+    w = weights(g)
+    fe, shape = frames(f.b, f.ta, f.frame_lens, f.seed)
+    rng = np.random.Generator(np.random.PCG64(88000 + f.seed))
+    caps = np.zeros((f.b, f.cap_len), dtype=np.int64)
+    for i, n in enumerate(f.n_valid):
+        assert 1 <= n <= f.cap_len
+        caps[i, 0] = int(w["model.task_id_to_token_id"][(f.seed + i) % 7])
+        caps[i, 1:n] = 4 + (rng.random(n - 1) * g.n_words).astype(np.int64)
+    return fe, shape, torch.from_numpy(caps)
+
+
+def clean_clips(calls, b: int, margin: float = F16_MARGIN) -> List[int]:
+    """Clips whose every call has an effective margin above ``margin``: the f16 precision must decode them like the oracle."""
+    worst = [float("inf")] * b
+    for c in calls:
+        worst[c[1]] = min(worst[c[1]], effective_margin(c))
+    return [i for i in range(b) if worst[i] > margin]
+
+
+# clips of every search whose every call clears F16_MARGIN in the oracle's run (tests/test_cpu_decoder_geometry.py recounts them)
+CLEAN_CLIPS = {
+    ("v31_ff32_l2", "beam4_r1mod4"): 3, ("v31_ff32_l2", "beam8_r64"): 3, ("v31_ff32_l2", "beam16_generic"): 1,
+    ("v31_ff32_l2", "beam13_r65"): 1, ("v2048_ff96_l1", "beam1_r1"): 1, ("v2048_ff96_l1", "beam5_r35"): 7,
+    ("v2049_ff256_l6", "beam4_r2mod4"): 2, ("v2049_ff256_l6", "beam7_r63_short_mem"): 4, ("v2049_ff256_l6", "beam2_maxpred64"): 2,
+    ("v4096_ff1024_l2", "beam1_r3"): 3, ("v4096_ff1024_l2", "beam8_r8"): 1, ("v4096_ff1024_l2", "beam11_r33_generic"): 1,
+    ("v4097_ff1792_l1", "beam4_never_finishes"): 1, ("v4097_ff1792_l1", "beam5_r5"): 1, ("v6144_ff2048_l12", "beam1_r2"): 1,
+    ("v6144_ff2048_l12", "beam8_r24"): 1, ("v6145_ff2080_l2", "beam4_r36"): 8, ("v6145_ff2080_l2", "beam5_r10"): 2,
+    ("v8192_ff2304_l6", "beam1_r5"): 5, ("v8192_ff2304_l6", "beam8_r24"): 1, ("v8192_ff2304_l6", "beam9_generic"): 1,
+    ("v8193_ff4096_l2", "beam5_generic"): 2, ("v8193_ff4096_l2", "beam3_generic"): 2,
+}

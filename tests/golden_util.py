@@ -49,19 +49,25 @@ def first_risky_step(g, tol):
 
 
 def topk_at_reference_states(g, calls, eng, weights, cfg, forbid, tol, sum_atol, tag=""):
+    """``topk_at_states`` on a golden scenario ``g``: its frame embeddings, lengths, task tokens and search parameters."""
+    kw = json.loads(str(g["kw"]))
+    tasks = json.loads(str(g["tasks"]))
+    task_names = list(cfg["task_names"])
+    bos = weights["model.task_id_to_token_id"][torch.as_tensor([task_names.index(t) for t in tasks])].tolist()
+    return topk_at_states(calls, eng, torch.from_numpy(g["frame_embs"]), torch.from_numpy(g["audio_shape"][:, 1].astype(np.int32)), bos,
+                          kw.get("beam_size", cfg["beam_size"]), kw.get("min_pred_size", cfg["min_pred_size"]),
+                          kw.get("max_pred_size", cfg["max_pred_size"]), forbid, tol, sum_atol, tag)
+
+
+def topk_at_states(calls, eng, frame_embs, frame_lens, bos, beam, min_pred, max_pred, forbid, tol, sum_atol, tag=""):
     """Every _select_k_next_toks call of the reference's beam search (beam.py:230-269), checked INDEPENDENTLY of the others: the
     decoder kernels are fed the reference's own prefixes (teacher forcing through the KV-cached step kernels the search itself
     runs), the step's masking / log-softmax / running sums / flat top-k are restated here, and the picks must equal the
     reference's wherever its effective top-(k+1) margin exceeds `tol`.  calls: [(step, clip, parents, tokens, sums, margin)] in
-    the reference's call order.  Returns (calls above the margin verified, calls identical incl. near-ties, calls above the margin)."""
-    kw = json.loads(str(g["kw"]))
-    bsz = len(g["lengths"])
-    beam = kw.get("beam_size", cfg["beam_size"])
-    min_pred = kw.get("min_pred_size", cfg["min_pred_size"])
-    max_pred = kw.get("max_pred_size", cfg["max_pred_size"])
-    tasks = json.loads(str(g["tasks"]))
-    task_names = list(cfg["task_names"])
-    bos = weights["model.task_id_to_token_id"][torch.as_tensor([task_names.index(t) for t in tasks])].tolist()
+    the reference's call order; frame_embs (B, T, 768), frame_lens (B,), bos: the B first tokens; forbid (V,) bool or None.
+    Returns (calls above the margin verified, calls identical incl. near-ties, calls above the margin)."""
+    bsz = int(frame_embs.shape[0])
+    bos = [int(t) for t in bos]
     v = eng.vocab_size
     forbid = torch.zeros(v, dtype=torch.bool) if forbid is None else forbid.bool()
     state = {j: ([[bos[j]] for _ in range(beam)], [0.0] * beam) for j in range(bsz)}
@@ -76,8 +82,8 @@ def topk_at_reference_states(g, calls, eng, weights, cfg, forbid, tol, sum_atol,
         newp = [pre[p_] + [t] for p_, t in zip(par, tok)]
         keep = [i for i, t in enumerate(tok) if not (t == 2 or step == max_pred - 1)]
         state[clip] = ([newp[i] for i in keep], [sums[i] for i in keep])
-    fe = torch.from_numpy(g["frame_embs"])[rows_clip].cuda()
-    lens = torch.from_numpy(g["audio_shape"][:, 1].astype(np.int32))[rows_clip]
+    fe = frame_embs[rows_clip].cuda()
+    lens = frame_lens.to(torch.int32)[rows_clip]
     caps = torch.as_tensor(rows_caps, dtype=torch.int64)
     eng.set_forcing_stepwise(True)   # the KV-cached step kernels the search itself runs (fused block / FFN kernels in bf16)
     try:

@@ -1,0 +1,339 @@
+"""GPU: the decoder and search kernels at every vocabulary, FFN, layer-count, row-count and memory-length edge of
+tests/decoder_geometry.py, against the CPU oracle run inside the test (oracle/cpu_ref.py; oracle/bf16_ref.py for the 16-bit
+operand precisions).  tests/test_cpu_decoder_geometry.py proves that the table reaches every regime and that every search is
+decided by margins of at least 2e-3, so the exact precisions are compared call by call without any near-tie allowance.
+
+Per geometry (a module-scoped fixture: its engines are created lazily and dropped when pytest moves to the next geometry):
+  a. search, fp32 / exact: every call's parents, tokens and order, running sums, captions, sizes and scores; greedy at beam 1
+  b. teacher-forcing logits, all four precisions x {fused step kernels, one launch per sub-layer, one pass} against the
+     precision's own oracle; the 16-bit top-k of every call at the oracle's states; the sequential 16-bit search
+  c. state independence, bf16 / exact: poisoned workspaces, a clip alone against the clip in its batch, eager / capture / replay
+"""
+import gc
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import decoder_geometry as D
+from tests import golden_util as G
+
+pytestmark = pytest.mark.gpu
+
+EXACT = ("fp32", "exact")
+R16 = D.R16
+ROUNDING = {"bf16": 1.0, "f16": 0.125}      # tests/block_oracle.py ROUNDING: operand rounding relative to bf16
+
+# Worst |logit error| of the 16-bit precisions against their own operand oracle at the two geometries deeper / wider than the
+# 6-layer x 2048 decoder the inherited bounds were measured at: (measured max, measured mean) on MI355X over the three modes; the
+# test holds a build to TWICE these, and the bound may not exceed the case's own oracle-to-fp32-oracle distance (an error
+# beyond that distance is not operand rounding).
+FORCING_MEASURED = {
+    ("v6144_ff2048_l12", "bf16"): (0.12338, 0.01029), ("v6144_ff2048_l12", "f16"): (0.02052, 0.001577),
+    ("v8193_ff4096_l2", "bf16"): (0.0668, 0.002813), ("v8193_ff4096_l2", "f16"): (0.01206, 0.000747),
+}
+
+
+class _Geo:
+    """One decoder geometry: its engines (lazily, per precision), its oracle runs (once, shared by the tests, never modified)."""
+
+    def __init__(self, g):
+        self.g = g
+        self.engines = {}
+        self.cache = {}
+        self.side = torch.cuda.Stream()
+        torch.set_num_threads(min(16, os.cpu_count() or 1))
+
+    def engine(self, prec):
+        if prec not in self.engines:
+            from conette_amd.engine import Engine
+            self.engines[prec] = Engine(D.weights(self.g), precision=prec, n_layers=self.g.n_layers, d_ff=self.g.d_ff)
+        return self.engines[prec]
+
+    def oracle(self, s):
+        if ("search", s.name) not in self.cache:
+            self.cache[("search", s.name)] = D.oracle_search(self.g, s)
+        return self.cache[("search", s.name)]
+
+    def greedy_ref(self, s):
+        if ("greedy", s.name) not in self.cache:
+            from oracle import cpu_ref as O
+            ref = self.oracle(s)
+            _, _, bos, forbid = D.search_inputs(self.g, s)
+            self.cache[("greedy", s.name)] = O.greedy_search(D.weights(self.g), ref["mem"], ref["mask"], bos, vocab_size=self.g.v,
+                                                               min_pred_size=s.min_pred, max_pred_size=s.max_pred, forbid_rep_mask=forbid,
+                                                               n_layers=self.g.n_layers)
+        return self.cache[("greedy", s.name)]
+
+    def forcing_ref(self, kind):
+        """logits (B, V, cap_len) of the forcing case: kind "fp32" (oracle/cpu_ref.py) or "bf16" / "f16" (oracle/bf16_ref.py)"""
+        if ("forcing", kind) not in self.cache:
+            from oracle import bf16_ref as Bf
+            from oracle import cpu_ref as O
+            fe, shape, caps = D.forcing_inputs(self.g, self.g.forcing)
+            if kind == "fp32":
+                ref = O.teacher_forcing(D.weights(self.g), fe, shape, caps, n_layers=self.g.n_layers)
+            else:
+                with Bf.operands(kind):
+                    ref = Bf.teacher_forcing_bf16(D.weights(self.g), fe, shape, caps, n_layers=self.g.n_layers)
+            self.cache[("forcing", kind)] = ref.numpy()
+        return self.cache[("forcing", kind)]
+
+    def decode(self, prec, s, fe=None, shape=None, bos=None, **kw):
+        fe0, shape0, bos0, forbid = D.search_inputs(self.g, s)
+        fe, shape, bos = (fe0 if fe is None else fe), (shape0 if shape is None else shape), (bos0 if bos is None else bos)
+        # on a side stream (the legacy default stream cannot be captured): the first sighting of a shape runs eagerly, the second is
+        # captured into a hipGraph, later ones replay it -- the tests that decode a case several times cross all three
+        self.side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.side):
+            out = self.engine(prec).decode(fe.cuda(), shape[:, 1].int(), bos, forbid, s.beam, s.min_pred, s.max_pred, want_trace=True, **kw)
+        torch.cuda.synchronize()
+        return {k: v.cpu() for k, v in out.items()}
+
+
+@pytest.fixture(scope="module", params=[g.name for g in D.GEOMETRIES])
+def geo(request):
+    h = _Geo(D.geometry(request.param))
+    yield h
+    h.engines.clear()
+    h.cache.clear()
+    D.drop_weights(h.g)
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def _assert_bit_equal(a, b, what):
+    for k in a:
+        assert torch.equal(_bits(a[k]), _bits(b[k])), (what, k)
+
+
+# ---- a. search against the oracle: fp32 and exact -------------------------------------------------------------------------------
+@pytest.mark.parametrize("prec", EXACT)
+def test_search_matches_the_oracle(prec, geo):
+    """Every search of the geometry: every call's parents, tokens and order equal the oracle's (no near-tie allowance: every
+    effective margin is >= 2e-3), running sums to 2e-4 x (step + 1), captions and sizes identical, scores to 1e-4; at beam 1 also
+    conette_greedy against the oracle's greedy search (finite pattern, arg-max chain, finite logits rtol 1e-3 / atol 2e-3)."""
+    g = geo.g
+    for s in g.searches:
+        tag = (g.name, s.name, prec, D.search_kernel(g.v, s.beam), D.ffn_regime(prec, g.d_ff))
+        ref = geo.oracle(s)
+        out = geo.decode(prec, s)
+        sel, val = out["trace_sel"].numpy(), out["trace_val"].numpy()
+        for step, clip, par, tok, sums, margin in ref["calls"]:
+            k = len(par)
+            assert sel[step, clip, :k, 0].tolist() == par and sel[step, clip, :k, 1].tolist() == tok, (tag, step, clip, sel[step, clip, :k].tolist(), par, tok)
+            np.testing.assert_allclose(val[step, clip, :k], sums, rtol=0, atol=2e-4 * (step + 1), err_msg=str((tag, step, clip)))
+        ps, bm = (int(x) for x in out["sizes"].tolist())
+        assert [ps, bm] == [ref["mult_preds"].shape[2], ref["best_preds"].shape[1]], tag
+        assert out["mult_preds"][:, :, :ps].tolist() == ref["mult_preds"].tolist(), tag
+        assert out["best_preds"][:, :bm].tolist() == ref["best_preds"].tolist(), tag
+        np.testing.assert_allclose(out["mult_lprobs"].numpy(), ref["mult_lprobs"].numpy(), rtol=0, atol=1e-4, err_msg=str(tag))
+        np.testing.assert_allclose(out["best_lprobs"].numpy(), ref["best_lprobs"].numpy(), rtol=0, atol=1e-4, err_msg=str(tag))
+        if s.beam == 1:
+            fe, shape, bos, forbid = D.search_inputs(g, s)
+            gr = geo.engine(prec).greedy(fe.cuda(), shape[:, 1].int(), bos, forbid, s.min_pred, s.max_pred)
+            got, want = gr["logits"].permute(0, 2, 1).cpu(), geo.greedy_ref(s)
+            assert tuple(got.shape) == tuple(want.shape), tag
+            fin = torch.isfinite(want)
+            assert torch.equal(torch.isfinite(got), fin), tag
+            np.testing.assert_allclose(got[fin].numpy(), want[fin].numpy(), rtol=1e-3, atol=2e-3, err_msg=str(tag))
+            assert torch.equal(got.argmax(dim=1), want.argmax(dim=1)), tag
+            assert torch.equal(gr["preds"].cpu().long(), got.argmax(dim=1)), tag
+
+
+# ---- b. logits against the precision's own oracle -----------------------------------------------------------------------------
+MODES = ("step_fused", "step_unfused", "onepass")
+
+
+def _forcing(eng, mode, fe, lens, caps):
+    eng.set_decode_fusion(mode == "step_fused")
+    eng.set_forcing_stepwise(mode != "onepass")
+    try:
+        return eng.forcing(fe.cuda(), lens, caps).permute(0, 2, 1).cpu().numpy()      # (B, V, cap_len) like the oracles
+    finally:
+        eng.set_decode_fusion(True)
+        eng.set_forcing_stepwise(False)
+
+
+@pytest.mark.parametrize("prec", D.PRECISIONS)
+def test_forcing_logits_match_the_precisions_oracle(prec, geo):
+    """The forcing case of the geometry through the fused step kernels, the per-sub-layer step kernels and the one-pass kernels.
+    fp32 / exact against oracle/cpu_ref.py: rtol 1e-3, atol 2e-3.  bf16 / f16 against oracle/bf16_ref.py at the same operand
+    type: rtol 3e-3 k, atol 0.15 min(1, 2k), mean < 0.03 min(1, 2k) (k = 1 / 0.125: the bounds of
+    test_gpu_bf16_parity.py::test_teacher_forcing_against_bf16_operand_oracle, measured at 6 layers x 2048), unchanged for every
+    geometry no deeper and with d_ff < 4096.  The 12-layer and the 4096-wide geometries are held to twice what they measured on
+    MI355X (FORCING_MEASURED; worst of the three modes) or, where that is less, to the distance between the operand oracle and
+    the fp32 oracle on the same case (computed here: 0.258 / 0.034 for bf16 / f16 at 12 layers, 0.169 / 0.024 at d_ff = 4096).
+    In every geometry the kernels must sit closer to their operand oracle than that oracle sits to the fp32 one."""
+    g, f = geo.g, geo.g.forcing
+    fe, shape, caps = D.forcing_inputs(g, f)
+    valid = (caps.numpy() != 0)[:, None, :]
+    eng = geo.engine(prec)
+    ref32 = geo.forcing_ref("fp32")
+    ref = ref32 if prec in EXACT else geo.forcing_ref(prec)
+    dist = float(np.abs((ref - ref32) * valid).max())
+    errs = {}
+    for mode in MODES:
+        tag = (g.name, f.name, prec, mode, D.ffn_regime(prec, g.d_ff, mode == "step_fused") if mode != "onepass" else "onepass")
+        got = _forcing(eng, mode, fe, shape[:, 1].int(), caps)
+        assert got.shape == ref.shape and np.isfinite(got * valid).all(), tag
+        errs[tag] = (got, np.abs(got - ref) * valid)
+        print(f"forcing {tag}: max {errs[tag][1].max():.5f} mean {errs[tag][1].mean():.6f}; operand oracle to fp32 oracle {dist:.5f}")
+    for tag, (got, err) in errs.items():
+        if prec in EXACT:
+            np.testing.assert_allclose(got * valid, ref * valid, rtol=1e-3, atol=2e-3, err_msg=str(tag))
+            continue
+        k = ROUNDING[prec]
+        assert float(err.max()) < dist, (tag, float(err.max()), dist)      # closer to its own oracle than that oracle is to fp32
+        if g.name in D.MEASURED_BOUND_GEOMETRIES:
+            m_max, m_mean = FORCING_MEASURED[(g.name, prec)]
+            assert err.max() <= min(2 * m_max, dist) and err.mean() <= 2 * m_mean, (tag, float(err.max()), float(err.mean()), dist)
+        else:
+            np.testing.assert_allclose(got * valid, ref * valid, rtol=3e-3 * k, atol=0.15 * min(1.0, 2 * k), err_msg=str(tag))
+            assert err.mean() < 0.03 * min(1.0, 2 * k), (tag, float(err.mean()))
+
+
+@pytest.mark.parametrize("prec", D.H16)
+def test_topk_at_the_oracles_states_16bit(prec, geo):
+    """Every call of every search, fed the oracle's own prefixes: wherever the oracle's effective margin exceeds 0.25 x R16 the
+    picks, their parents and their order are the oracle's (none skipped), and the running sums agree to 0.2 x R16."""
+    g = geo.g
+    for s in g.searches:
+        ref = geo.oracle(s)
+        fe, shape, bos, forbid = D.search_inputs(g, s)
+        tol = 0.25 * R16[prec]
+        n_checked, n_same, n_eligible = G.topk_at_states(ref["calls"], geo.engine(prec), fe, shape[:, 1], bos.tolist(), s.beam, s.min_pred,
+                                                         s.max_pred, forbid, tol, sum_atol=lambda step: 0.2 * R16[prec],
+                                                         tag=(g.name, s.name, prec))
+        print(f"top-k at the oracle's states {g.name}/{s.name}/{prec}: {n_checked} of {len(ref['calls'])} calls above the margin verified, "
+              f"{n_same} identical")
+        assert n_checked == n_eligible == sum(1 for c in ref["calls"] if D.effective_margin(c) > tol), (g.name, s.name, prec)
+        if prec == "f16":
+            assert n_eligible >= 1, (g.name, s.name)
+
+
+@pytest.mark.parametrize("prec", D.H16)
+def test_sequential_search_16bit(prec, geo):
+    """The 16-bit search itself.  A clip whose every call clears 0.25 x R16 in the oracle's run (for f16 the clips counted by
+    tests/test_cpu_decoder_geometry.py: at least one per search) must match the oracle end to end: every call, the captions in
+    their slots, scores within 0.05 x R16.  The other clips are compared call by call until their first sub-tolerance call falls
+    the other way.  Running sums: every step adds one log-probability, which the test above holds to 0.2 x R16 at the oracle's
+    states, hence 0.2 x R16 x (step + 1).  (The 0.12 per step that tests/test_gpu_parity.py holds the golden fixtures' beams of at
+    most 8 to is exceeded here by the low-ranked picks of the wide beams: 0.147 at step 0 of beam 11 at V = 4096 and 0.138 at beam 9
+    at V = 8192, in bf16, against an operand-oracle-to-fp32 distance of 0.15 / 0.26 on those geometries.)"""
+    g = geo.g
+    for s in g.searches:
+        ref = geo.oracle(s)
+        out = geo.decode(prec, s)
+        sel, val = out["trace_sel"].numpy(), out["trace_val"].numpy()
+        tol = 0.25 * R16[prec]
+        clean = D.clean_clips(ref["calls"], s.b, tol)
+        if prec == "f16":
+            assert len(clean) == D.CLEAN_CLIPS[(g.name, s.name)] >= 1, (g.name, s.name, clean)
+        diverged, n_checked, n_tie = set(), 0, 0
+        for step, clip, par, tok, sums, margin in ref["calls"]:
+            if clip in diverged:
+                continue
+            k = len(par)
+            same = sel[step, clip, :k, 0].tolist() == par and sel[step, clip, :k, 1].tolist() == tok
+            if D.effective_margin((step, clip, par, tok, sums, margin)) <= tol:
+                n_tie += 1
+                if not same:
+                    diverged.add(clip)
+                continue
+            assert same, (g.name, s.name, prec, step, clip, sel[step, clip, :k].tolist(), par, tok)
+            np.testing.assert_allclose(val[step, clip, :k], sums, rtol=0, atol=0.2 * R16[prec] * (step + 1))
+            n_checked += 1
+        assert not (diverged & set(clean)), (g.name, s.name, prec, diverged, clean)
+        ps = ref["mult_preds"].shape[2]
+        for clip in clean:
+            assert out["mult_preds"][clip, :, :ps].tolist() == ref["mult_preds"][clip].tolist(), (g.name, s.name, prec, clip)
+            assert not out["mult_preds"][clip, :, ps:].any()
+            bm = ref["best_preds"].shape[1]
+            assert out["best_preds"][clip, :bm].tolist() == ref["best_preds"][clip].tolist(), (g.name, s.name, prec, clip)
+            np.testing.assert_allclose(out["mult_lprobs"][clip].numpy(), ref["mult_lprobs"][clip].numpy(), rtol=0, atol=0.05 * R16[prec])
+            np.testing.assert_allclose(out["best_lprobs"][clip].numpy(), ref["best_lprobs"][clip].numpy(), rtol=0, atol=0.05 * R16[prec])
+        print(f"sequential search {g.name}/{s.name}/{prec}: {len(clean)} of {s.b} clips end to end, {n_checked} of {len(ref['calls'])} calls "
+              f"checked, {n_tie} below the margin, diverged clips {sorted(diverged)}")
+
+
+# ---- c. state independence --------------------------------------------------------------------------------------------------
+def _poison(eng, byte):
+    """every cached decode workspace and I/O buffer of the engine (inputs are rewritten by the next call)"""
+    for t in eng._ws.values():
+        t.fill_(byte)
+    for buf in eng._dec_bufs.values():
+        for t in buf.values():
+            if t is not None:
+                t.view(torch.uint8).fill_(byte)
+
+
+@pytest.mark.parametrize("prec", ("bf16", "exact"))
+def test_search_does_not_depend_on_stale_memory(prec, geo):
+    """Workspaces and output buffers full of 0xFF bytes (NaN as floats, -1 as ids), then full of zeros: every output and the
+    trace are bit-equal -- nothing is read before it is written, and nothing is left unwritten."""
+    g = geo.g
+    eng = geo.engine(prec)
+    for s in g.searches:
+        first = geo.decode(prec, s)
+        _poison(eng, 0xFF)
+        a = geo.decode(prec, s)
+        _poison(eng, 0)
+        b = geo.decode(prec, s)
+        _assert_bit_equal(first, a, (g.name, s.name, prec, "0xFF"))
+        _assert_bit_equal(first, b, (g.name, s.name, prec, "zeros"))
+
+
+@pytest.mark.parametrize("prec", ("bf16", "exact"))
+def test_clip_alone_equals_clip_in_batch(prec, geo):
+    """Each clip of the geometry's first ragged batch decoded alone: ids and trace equal the batch's; scores bit-equal where the
+    fused FFN kernel runs (block and FFN kernels are row-local), within 2e-5 through the other paths and with fusion off."""
+    g = geo.g
+    s = next(s for s in g.searches if s.b > 1 and len(set(s.frame_lens)) > 1)
+    fe, shape, bos, _ = D.search_inputs(g, s)
+    eng = geo.engine(prec)
+    for fusion in (True, False):
+        eng.set_decode_fusion(fusion)
+        try:
+            full = geo.decode(prec, s)
+            for i in range(s.b):
+                one = geo.decode(prec, s, fe=fe[i:i + 1].contiguous(), shape=shape[i:i + 1], bos=bos[i:i + 1])
+                tag = (g.name, s.name, prec, fusion, i)
+                assert torch.equal(one["mult_preds"][0], full["mult_preds"][i]) and torch.equal(one["best_preds"][0], full["best_preds"][i]), tag
+                assert torch.equal(one["trace_sel"][:, 0], full["trace_sel"][:, i]), tag
+                if fusion and D.ffn_regime(prec, g.d_ff).startswith("fused"):
+                    assert torch.equal(_bits(one["mult_lprobs"][0]), _bits(full["mult_lprobs"][i])), tag
+                    assert torch.equal(_bits(one["best_lprobs"][0]), _bits(full["best_lprobs"][i])), tag
+                    assert torch.equal(_bits(one["trace_val"][:, 0]), _bits(full["trace_val"][:, i])), tag
+                else:
+                    np.testing.assert_allclose(one["mult_lprobs"][0].numpy(), full["mult_lprobs"][i].numpy(), rtol=0, atol=2e-5, err_msg=str(tag))
+                    np.testing.assert_allclose(one["best_lprobs"][0].numpy(), full["best_lprobs"][i].numpy(), rtol=0, atol=2e-5, err_msg=str(tag))
+        finally:
+            eng.set_decode_fusion(True)
+
+
+@pytest.mark.parametrize("prec", ("bf16", "exact"))
+def test_eager_capture_and_replay_agree(prec, geo):
+    """One decode with the hipGraph disabled, then three with it enabled on a context that has no graph yet (the first sighting of
+    a key runs eagerly, the second is captured, the third replays): four bit-equal results."""
+    g = geo.g
+    eng = geo.engine(prec)
+    for s in g.searches:
+        eng.set_decode_fusion(True)          # (drops every cached graph of the context)
+        eng.set_decode_graph(False)
+        try:
+            runs = [geo.decode(prec, s)]
+        finally:
+            eng.set_decode_graph(True)
+        nodes = []
+        for _ in range(3):
+            runs.append(geo.decode(prec, s))
+            nodes.append(eng.decode_graph_nodes())
+        for i in range(1, 4):
+            _assert_bit_equal(runs[0], runs[i], (g.name, s.name, prec, "run", i))
+        assert nodes[1] > 0 and nodes[2] == nodes[1], (g.name, s.name, nodes)
