@@ -12,18 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libconette_hip.so")
 SOURCES = ["api.hip", "frontend.hip", "encoder.hip", "decoder.hip"]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-DCN_RC2_GELU_PK"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 if os.environ.get("CN_G2_PROF"):  # profiling build: phase stamps inside the encoder GEMM (tools/g2prof.py)
     FLAGS.append("-DCN_G2_PROF")
-if os.environ.get("CN_NO_RS"):     # A/B build: the chained stage-2 kernel of round 2 instead of the role-split one
-    FLAGS.append("-DCN_NO_RS")
 for knob in ("FE_NOFILL", "FE_POISON", "FE_NW", "FE_VARIANT"):   # lab builds of the log-mel kernel (tools/lab/logmel_repro.sh)
     if os.environ.get(knob):
         FLAGS.append(f"-D{knob}" + ("" if os.environ[knob] == "1" and knob != "FE_NW" else "=" + os.environ[knob]))
 if os.environ.get("CN_EXTRA_FLAGS"):   # lab builds: extra compiler flags for every file (e.g. -fno-slp-vectorize)
     FLAGS += os.environ["CN_EXTRA_FLAGS"].split()
-if os.environ.get("CN_NO_SAT8"):   # A/B build: fp16 GELU outputs of the fused MLP without the saturating v_pk_min_f16
-    FLAGS.append("-DCN_NO_SAT8")
 if os.environ.get("CN_DB_ROWS"):   # A/B build: rows per decoder block kernel (dec_block.h: 4)
     FLAGS.append("-DDB_ROWS=" + os.environ["CN_DB_ROWS"])
 if os.environ.get("CN_DB_ROWS_SP"):   # A/B build: rows per decoder block kernel in the exact precision (dec_block.h: 4)
@@ -36,19 +32,9 @@ if os.environ.get("CN_DB_WIDE_R"):      # A/B build: rows from which a search co
     FLAGS.append("-DDB_WIDE_R=" + os.environ["CN_DB_WIDE_R"])
 if os.environ.get("CN_DB_XCDS"):   # A/B build: XCDs whose workgroups work in the decoder block kernel (dec_block.h: 8 = all)
     FLAGS.append("-DDB_XCDS=" + os.environ["CN_DB_XCDS"])
-if os.environ.get("CN_G2_NOACT"):
-    FLAGS.append("-DCN_G2_NOACT")
-if os.environ.get("CN_RS_PRIO"):    # A/B build: static wave priority in the role-split fused MLP (encoder.hip: 8 = B waves)
-    FLAGS.append("-DCN_RS_PRIO=" + os.environ["CN_RS_PRIO"])
-if os.environ.get("CN_RS16"):       # A/B build: 0 = stage 2 of the bf16 / f16 precisions on the 32x32x16 role-split kernel (mlp_rs.h)
-    FLAGS.append("-DCN_RS16=" + os.environ["CN_RS16"])
-if os.environ.get("CN_STEM_MFMA"):  # A/B build: 0 = the VALU stem kernel
-    FLAGS.append("-DCN_STEM_MFMA=" + os.environ["CN_STEM_MFMA"])
 for _k in ("CN_DW96_S", "CN_DW96_TH", "CN_DW192_S", "CN_DW192_TH"):   # A/B builds: tile of the depthwise kernel of stages 0 / 1 (encoder.hip)
     if os.environ.get(_k):
         FLAGS.append(f"-D{_k}=" + os.environ[_k])
-if os.environ.get("CN_DW_DOT2"):    # A/B build: 0 = the depthwise conv of the fp16 stream with one v_fma_mix_f32 per tap (encoder.hip)
-    FLAGS.append("-DCN_DW_DOT2=" + os.environ["CN_DW_DOT2"])
 if os.environ.get("CN_FW_SPLIT"):   # A/B build: threads per channel of the full-width depthwise kernel at C = 384 (encoder.hip: 2)
     FLAGS.append("-DCN_FW_SPLIT=" + os.environ["CN_FW_SPLIT"])
 if os.environ.get("CN_FW_TH"):      # A/B build: output rows per block of the full-width depthwise kernel at C = 384 (encoder.hip: 4)

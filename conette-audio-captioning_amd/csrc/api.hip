@@ -10,7 +10,6 @@
 #include "ctx.h"
 #include <algorithm>
 #include "mlp_rc2.h"
-#include "mlp_rs.h"
 #include "mlp_rs16.h"
 #include "mlp_sp.h"
 #include "down_fused.h"
@@ -104,7 +103,7 @@ __global__ void pk_taps_last(const float* __restrict__ src, float* __restrict__ 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < C * taps) dst[(i % taps) * C + i / taps] = src[i];
 }
-// depthwise (C, 1, 7, 7) -> [42][C] fp16 pairs of consecutive kernel rows (encoder.hip, CN_DW_DOT2): slot a * 7 + j = (k[2a][j], k[2a+1][j]),
+// depthwise (C, 1, 7, 7) -> [42][C] fp16 pairs of consecutive kernel rows (encoder.hip, the v_dot2 path of the fp16 stream): slot a * 7 + j = (k[2a][j], k[2a+1][j]),
 // slot 21 + a * 7 + j = (k[2a+1][j], k[2a+2][j]), a < 3; the low half is the first of the pair
 __global__ void pk_dw_pairs(const float* __restrict__ src, unsigned* __restrict__ dst, int C) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -480,24 +479,21 @@ extern "C" int conette_create(const conette_config* cfg, int32_t n_tensors, cons
           if (w1 && w2 && bw.b1 && bw.b2 && bw.scale && cn_pack_mlp_sp(w1, bw.b1, w2, bw.b2, bw.scale, C, ms, 0) == CN_OK) bw.mlp_sp = ms;
         }
         if (ctx->esize == 2 && C <= 384) {
-          // Rc2Geom<C, 1>::TOTAL_BYTES; the role-split streams of C = 384 are [C/8][C/8 + 1] KB (mlp_rs.h) or [C/8][C/8 + 2] KB
-          // (mlp_rs16.h) + C fp32
-          const size_t bytes = std::max((size_t)(C / 8) * (C / 8 + 1) * 1024 + (size_t)(C / 32) * 1024, (size_t)(C / 8) * (C / 8 + 2) * 1024 + (size_t)C * 4);
+          // the packed stream of the kernel that runs at this C (encoder.hip): role-split at C = 384 (mlp_rs16.h), register-chained
+          // below (mlp_rc2.h; the stream has the same size for NCK = 1 and 2)
+          const size_t bytes = C == 384 ? Rs16Geom<384>::TOTAL_BYTES : C == 192 ? Rc2Geom<192, 1>::TOTAL_BYTES : Rc2Geom<96, 1>::TOTAL_BYTES;
           void* ms = B.alloc(bytes);
           const float* w1 = B.find(p + "pwconv1.weight", (int64_t)4 * C * C);
           const float* w2 = B.find(p + "pwconv2.weight", (int64_t)4 * C * C);
           if (w1 && w2 && bw.b1 && bw.b2 && bw.scale) {
-            const int units = ((C / 8) * (C / 8 + 1) + C / 32) * 64;  // one thread per 16-byte fragment piece, the bias fragments included
-            // C = 384 runs the role-split kernel (mlp_rs.h): same fragments, entry e = [W1 of chunk e | W2 of chunk e - 2]
-#ifndef CN_NO_RS
-            // (with the 16-bit residual stream of the bf16 / f16 precisions: mlp_rs16.h, the same pipeline on 16x16x32 MFMAs)
-            if (C == 384 && CN_RS16) {
+            // one thread per 16-byte fragment piece
+            if (C == 384) {  // ring entry e = [W1 of chunk e | b1 | W2 of chunk e - 2]
               const int u16 = (C / 8) * (C / 8 + 2) * 64;
               CN_H16_CALL(ctx, hipLaunchKernelGGL(pk_mlp_rs16<HT>, dim3((u16 + 255) / 256), dim3(256), 0, 0, w1, bw.b1, w2, bw.b2, bw.scale, C, (HT*)ms));
-            } else if (C == 384) CN_H16_CALL(ctx, hipLaunchKernelGGL(pk_mlp_rs<HT>, dim3((units + 255) / 256), dim3(256), 0, 0, w1, bw.b1, w2, bw.b2, bw.scale, C, (HT*)ms));
-            else
-#endif
-            CN_H16_CALL(ctx, hipLaunchKernelGGL(pk_mlp_rc2<HT>, dim3((units + 255) / 256), dim3(256), 0, 0, w1, bw.b1, w2, bw.b2, bw.scale, C, CN_RC2_NCK(C), (HT*)ms));
+            } else {
+              const int units = ((C / 8) * (C / 8 + 1) + C / 32) * 64;  // (the bias fragments included)
+              CN_H16_CALL(ctx, hipLaunchKernelGGL(pk_mlp_rc2<HT>, dim3((units + 255) / 256), dim3(256), 0, 0, w1, bw.b1, w2, bw.b2, bw.scale, C, CN_RC2_NCK(C), (HT*)ms));
+            }
             bw.mlp_stream = ms;
           }
         }

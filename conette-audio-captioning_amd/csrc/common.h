@@ -13,7 +13,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-#define CN_F32X16
 
 // ---- the two 16-bit operand types of the MFMA paths ------------------------------------------------------------------
 // bf16_t (CONETTE_PREC_BF16: 8 significant bits, fp32 range) and half_t (CONETTE_PREC_F16: IEEE fp16, 11 significant bits,
@@ -42,14 +41,12 @@ __device__ __forceinline__ f32x4 cn_mma16(cn_h8<half_t> a, cn_h8<half_t> b, f32x
 }
 // eight converted values that are known to be >= -65504 (GELU / ReLU outputs): +inf -> 65504 with four v_pk_min_f16
 template <typename H> __device__ __forceinline__ cn_h8<H> cn_sat8(cn_h8<H> v) {
-#ifndef CN_NO_SAT8  // (A/B builds only: what the saturation costs the fused MLP kernels)
   if constexpr (__is_same(H, half_t)) {
     cn_h8<H> m;
 #pragma unroll
     for (int i = 0; i < 8; ++i) m[i] = (H)65504.0f;
     return __builtin_elementwise_min(v, m);
   }
-#endif
   return v;
 }
 // eight fp32 values -> one 16-byte fragment (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32)
@@ -74,6 +71,23 @@ __device__ __forceinline__ void cn_dma16_v(const void* src_lane, unsigned lds) {
 // wave-uniform source base + 32-bit lane offset
 __device__ __forceinline__ void cn_dma16_s(const void* src_base, unsigned voff, unsigned lds) {
   asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src_base), "s"(lds) : "memory", "m0");
+}
+// s_waitcnt vmcnt(n) for a wave-uniform n (the immediate must be a constant); n >= 63: nothing to wait for (a wave never
+// has more than 63 vector-memory operations outstanding)
+__device__ __forceinline__ void cn_vm_wait(int n) {
+#define CN_VM_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
+  switch (n) {
+    CN_VM_CASE(0) CN_VM_CASE(1) CN_VM_CASE(2) CN_VM_CASE(3) CN_VM_CASE(4) CN_VM_CASE(5) CN_VM_CASE(6) CN_VM_CASE(7)
+    CN_VM_CASE(8) CN_VM_CASE(9) CN_VM_CASE(10) CN_VM_CASE(11) CN_VM_CASE(12) CN_VM_CASE(13) CN_VM_CASE(14) CN_VM_CASE(15)
+    CN_VM_CASE(16) CN_VM_CASE(17) CN_VM_CASE(18) CN_VM_CASE(19) CN_VM_CASE(20) CN_VM_CASE(21) CN_VM_CASE(22) CN_VM_CASE(23)
+    CN_VM_CASE(24) CN_VM_CASE(25) CN_VM_CASE(26) CN_VM_CASE(27) CN_VM_CASE(28) CN_VM_CASE(29) CN_VM_CASE(30) CN_VM_CASE(31)
+    CN_VM_CASE(32) CN_VM_CASE(33) CN_VM_CASE(34) CN_VM_CASE(35) CN_VM_CASE(36) CN_VM_CASE(37) CN_VM_CASE(38) CN_VM_CASE(39)
+    CN_VM_CASE(40) CN_VM_CASE(41) CN_VM_CASE(42) CN_VM_CASE(43) CN_VM_CASE(44) CN_VM_CASE(45) CN_VM_CASE(46) CN_VM_CASE(47)
+    CN_VM_CASE(48) CN_VM_CASE(49) CN_VM_CASE(50) CN_VM_CASE(51) CN_VM_CASE(52) CN_VM_CASE(53) CN_VM_CASE(54) CN_VM_CASE(55)
+    CN_VM_CASE(56) CN_VM_CASE(57) CN_VM_CASE(58) CN_VM_CASE(59) CN_VM_CASE(60) CN_VM_CASE(61) CN_VM_CASE(62)
+    default: break;
+  }
+#undef CN_VM_CASE
 }
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -275,7 +289,6 @@ template <int DEG> __device__ __forceinline__ float cn_gelu_e1_half(float h) {
   asm("" : "+v"(g));
   return g;
 }
-template <int DEG> __device__ __forceinline__ float cn_gelu_e1(float x) { return cn_gelu_e1_half<DEG>(0.5f * x); }
 
 // XCD-aware block remap (cdna guide T1, bijective form): workgroups are dealt round-robin over the
 // 8 XCDs, each with a private L2, so blocks b and b+8 share an L2.  Give every XCD one CONTIGUOUS

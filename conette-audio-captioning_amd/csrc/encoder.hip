@@ -22,120 +22,22 @@ __device__ __forceinline__ void cn_watch_stat(float v) {
 
 #include "gemm2.h"
 #include "mlp_rc2.h"
-#include "mlp_rs.h"
 #include "mlp_rs16.h"
 #include "mlp_sp.h"
 #include "down_fused.h"
 
-// fp16 stream: depthwise conv on row pairs through v_dot2_f32_f16 (0: A/B builds, one v_fma_mix_f32 per tap as in the first half of round 5)
-#ifndef CN_DW_DOT2
-#define CN_DW_DOT2 1
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // stem: Conv2d(1 -> 96, k 4x4, s 4x4, pad (4, 0)) + LayerNorm(channels_first, eps 1e-6)
-// in: logmel (B, F, 224) fp32; out: (B, H0, 56, 96) fp32.  4 lanes per output position (24 channels each, weights
-// read from LDS 16 bytes at a time); the 64 positions of a block are contiguous in the output, so the normalised
-// values go through an LDS tile and leave as whole 1 KB wave stores (16-byte pieces at a 96-byte lane stride made
-// the kernel store bound: 172 us for 403 MB).
+// in: logmel (B, F, 224) fp32; out: (B, H0, 56, 96) XT.
 // ---------------------------------------------------------------------------------------------
-template <int P, typename XT>  // P positions per lane group: the weights read from LDS (6 KB per position otherwise) are shared by P positions
-__global__ __launch_bounds__(256) void cn_stem_kernel(const float* __restrict__ in, int F, int H0, long n_pos,
-                                                      const float* __restrict__ w /*[16][96]*/,
-                                                      const float* __restrict__ bias, const float* __restrict__ ln_w,
-                                                      const float* __restrict__ ln_b, XT* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float s_w[16 * 96];
-  __shared__ __attribute__((aligned(16))) float s_o[P * 64 * 96];
-  for (int i = threadIdx.x; i < 16 * 96; i += 256) s_w[i] = w[i];
-  __syncthreads();
-  const int q = threadIdx.x & 3, lp = threadIdx.x >> 2;
-  const long pos0 = (long)blockIdx.x * (64 * P);
-  float xin[P][16];
-#pragma unroll
-  for (int u = 0; u < P; ++u) {
-    const long pos = pos0 + 64 * u + lp;
-    const long p = pos < n_pos ? pos : n_pos - 1;
-    const int wq = (int)(p % 56);
-    const long t = p / 56;
-    const int h = (int)(t % H0);
-    const int b = (int)(t / H0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = 4 * h - 4 + i;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (r >= 0 && r < F) v = *(const f32x4*)(in + ((size_t)b * F + r) * CN_N_MELS + 4 * wq);
-      xin[u][4 * i] = v[0], xin[u][4 * i + 1] = v[1], xin[u][4 * i + 2] = v[2], xin[u][4 * i + 3] = v[3];
-    }
-  }
-  f32x4 acc[P][6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const f32x4 b4 = *(const f32x4*)(bias + q * 24 + 4 * j);
-#pragma unroll
-    for (int u = 0; u < P; ++u) acc[u][j] = b4;
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const f32x4 w4 = *(const f32x4*)(s_w + i * 96 + q * 24 + 4 * j);
-#pragma unroll
-      for (int u = 0; u < P; ++u) acc[u][j] += xin[u][i] * w4;
-    }
-#pragma unroll
-  for (int u = 0; u < P; ++u) {
-    const f32x4 s4 = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]) + (acc[u][4] + acc[u][5]);
-    float s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    s += __shfl_xor(s, 1);
-    s += __shfl_xor(s, 2);
-    const float mean = s * (1.0f / 96.0f);
-    f32x4 q4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      acc[u][j] -= mean;
-      q4 += acc[u][j] * acc[u][j];
-    }
-    float v2 = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-    v2 += __shfl_xor(v2, 1);
-    v2 += __shfl_xor(v2, 2);
-    const float rstd = 1.0f / sqrtf(v2 * (1.0f / 96.0f) + 1e-6f);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int ch = q * 24 + 4 * j;
-      *(f32x4*)(s_o + (64 * u + lp) * 96 + ch) = acc[u][j] * rstd * *(const f32x4*)(ln_w + ch) + *(const f32x4*)(ln_b + ch);
-    }
-  }
-  __syncthreads();
-  if constexpr (sizeof(XT) == 2) {
-    const long n8 = min((long)(64 * P), n_pos - pos0) * 12;  // 16-byte pieces (8 values) of this block's positions
-    cn_h8<XT>* o8 = (cn_h8<XT>*)(out + (size_t)pos0 * 96);
-#pragma unroll
-    for (int k = 0; k < 3 * P; ++k) {
-      const int i = threadIdx.x + 256 * k;
-      if (i < n8) {
-        const f32x4 a = ((const f32x4*)s_o)[2 * i], b = ((const f32x4*)s_o)[2 * i + 1];
-        o8[i] = cn_h8<XT>{cn_from_f32<XT>(a[0]), cn_from_f32<XT>(a[1]), cn_from_f32<XT>(a[2]), cn_from_f32<XT>(a[3]),
-                          cn_from_f32<XT>(b[0]), cn_from_f32<XT>(b[1]), cn_from_f32<XT>(b[2]), cn_from_f32<XT>(b[3])};
-      }
-    }
-  } else {
-  const long n4 = min((long)(64 * P), n_pos - pos0) * 24;  // 16-byte pieces of this block's positions
-  f32x4* o4 = (f32x4*)(out + (size_t)pos0 * 96);
-#pragma unroll
-  for (int k = 0; k < 6 * P; ++k) {
-    const int i = threadIdx.x + 256 * k;
-    if (i < n4) o4[i] = ((const f32x4*)s_o)[i];
-  }
-  }
-}
-
-// Stem on the fp32 matrix cores (round 5).  The VALU kernel above reads its 16 x 96 weights from LDS once per position (6 KB, 69 us
-// of LDS time per launch at B = 64: it is LDS bound); here the product runs transposed as O^T = W^T (96 x 16) . patches^T (16 x 32
-// positions) on v_mfma_f32_32x32x2_f32 -- exact fp32 products and sums -- with W^T as 24 A-operand registers per lane, loaded once
-// per wave: no weights in LDS at all.  Lane (j = l & 31, h = l >> 5) is position tile * 32 + j; k-step s of the product takes
-// patch row s >> 1, columns 2 h + (s & 1): one 8-byte load per patch row and lane.  The rows of W^T are permuted (cn_rc2_chan) so that
-// accumulator register r of channel tile t is channel 32 t + 16 (r >> 3) + 8 h + (r & 7): a lane owns 48 channels of ITS position in
-// runs of eight, the LayerNorm statistics are a lane sum plus one exchange between the halves, the stores are 16 bytes.
+// On the fp32 matrix cores since round 5.  (The VALU kernel of rounds 1-4 -- git history -- read its 16 x 96 weights from LDS once
+// per position: 6 KB, 69 us of LDS time per launch at B = 64, it was LDS bound.)  Here the product runs transposed as
+// O^T = W^T (96 x 16) . patches^T (16 x 32 positions) on v_mfma_f32_32x32x2_f32 -- exact fp32 products and sums -- with W^T as 24
+// A-operand registers per lane, loaded once per wave: no weights in LDS at all.  Lane (j = l & 31, h = l >> 5) is position
+// tile * 32 + j; k-step s of the product takes patch row s >> 1, columns 2 h + (s & 1): one 8-byte load per patch row and lane.
+// The rows of W^T are permuted (cn_rc2_chan) so that accumulator register r of channel tile t is channel
+// 32 t + 16 (r >> 3) + 8 h + (r & 7): a lane owns 48 channels of ITS position in runs of eight, the LayerNorm statistics are a
+// lane sum plus one exchange between the halves, the stores are 16 bytes.
 template <typename XT>
 __global__ __launch_bounds__(256) void cn_stem_mfma_kernel(const float* __restrict__ in, int F, int H0, long n_pos,
                                                            const float* __restrict__ w /*[16][96]*/, const float* __restrict__ bias,
@@ -299,7 +201,7 @@ __global__ __launch_bounds__((C > 384 ? 384 : C) * S) void cn_dwconv_ln_kernel(c
   // per-load 64-bit address arithmetic that dominated the VALU instruction count (rocprof:
   // 4250 VALU wave-instructions per 32-output patch against 1568 FMAs).
   const bool interior = (h0 >= 3) && (h0 + TH + 3 <= H) && (w0 >= 3) && (w0 + 4 + 3 <= W);
-  if constexpr (sizeof(XT) == 2 && CN_DW_DOT2) {
+  if constexpr (sizeof(XT) == 2) {
     // ---- fp16 stream, round 5: input rows in PAIRS.  p[q] = (x[r][q], x[r + 1][q]) for even r is one register, the weights come as
     // fp16 pairs of consecutive kernel rows -- ke[a][j] = (k[2a][j], k[2a + 1][j]), ko[a][j] = (k[2a + 1][j], k[2a + 2][j]): whichever
     // parity r - oh has, the row pair meets a weight pair -- and `v_dot2_f32_f16` (exact fp16 products, fp32 sum) adds TWO taps per
@@ -424,7 +326,7 @@ __global__ __launch_bounds__((C > 384 ? 384 : C) * S) void cn_dwconv_ln_kernel(c
       fma_row(r, v);
     }
   }
-  }  // fp32 stream / CN_DW_DOT2 = 0
+  }  // fp32 stream
 #pragma unroll
   for (int oh = 0; oh < TH; ++oh)
 #pragma unroll
@@ -565,7 +467,7 @@ __device__ __forceinline__ void cn_fw_conv(const XT* __restrict__ xb /* + c */, 
                                            const float* __restrict__ dw_w, const unsigned* __restrict__ dw_wp, float bias, int c,
                                            float* __restrict__ s_v, int PITCH) {
   constexpr int Q0 = OW0 - 3 < 0 ? 0 : OW0 - 3, Q1 = OW0 + NOW + 3 > WW ? WW : OW0 + NOW + 3, NQ = Q1 - Q0;
-  if constexpr (sizeof(XT) == 2 && CN_DW_DOT2) {
+  if constexpr (sizeof(XT) == 2) {
     // fp16 stream: input rows in pairs, two taps per v_dot2_f32_f16 (see cn_dwconv_ln_kernel)
     static_assert(TH % 2 == 0, "row pairs");
     cn_h2 ke[3][7], ko[3][7];
@@ -779,14 +681,8 @@ __global__ __launch_bounds__(C* SPLIT > 384 ? 768 : 384) void cn_dwconv_ln_fw_ke
 #ifndef CN_DW192_TH
 #define CN_DW192_TH 12
 #endif
-#ifndef CN_STEM_MFMA
-#define CN_STEM_MFMA 1   // 0 (A/B builds): the VALU stem kernel of rounds 1-4
-#endif
 #ifndef CN_FW_SPLIT
 #define CN_FW_SPLIT 2
-#endif
-#ifndef CN_RS_PRIO
-#define CN_RS_PRIO 8   // mlp_rs.h ABL bits 8 / 16: static wave priority for the B / the A role (0: none)
 #endif
 #ifndef CN_FW_TH
 #define CN_FW_TH 4   // output rows per block of the full-width kernel at C = 384 (A/B builds: 2 = half the LN tile, two blocks per CU)
@@ -1015,8 +911,8 @@ template <typename T, typename XT>
 static int dwconv_dispatch(int C, const XT* x, int B, int H, int W, const CnBlockW& bw, T* y, hipStream_t s) {
   switch (C) {
     // (the fp32 stream of the exact / fp32 precisions keeps 8-row tiles: its conv is bound by 49 fp32 multiply-adds per output)
-    case 96: return launch_dwconv<T, XT, 96, CN_DW96_S, (sizeof(XT) == 2 && CN_DW_DOT2) ? CN_DW96_TH : 8>(x, B, H, W, bw, y, s);
-    case 192: return launch_dwconv<T, XT, 192, CN_DW192_S, (sizeof(XT) == 2 && CN_DW_DOT2) ? CN_DW192_TH : 8>(x, B, H, W, bw, y, s);
+    case 96: return launch_dwconv<T, XT, 96, CN_DW96_S, sizeof(XT) == 2 ? CN_DW96_TH : 8>(x, B, H, W, bw, y, s);
+    case 192: return launch_dwconv<T, XT, 192, CN_DW192_S, sizeof(XT) == 2 ? CN_DW192_TH : 8>(x, B, H, W, bw, y, s);
     case 384:
       if (W == 14) return launch_dwconv_fw<T, XT, 384, 14, CN_FW_TH, CN_FW_SPLIT>(x, B, H, bw, y, s);
       return launch_dwconv<T, XT, 384, 1, 4>(x, B, H, W, bw, y, s);
@@ -1061,17 +957,10 @@ static int encode_impl(conette_ctx* ctx, const float* wave, int B, int L, float*
   {
     const long n_pos = (long)B * g.H[0] * g.W[0];
     CnProfScope ps(ctx, CONETTE_PROF_STEM, s);
-#if CN_STEM_MFMA
-    {
-      const long n_tiles = (n_pos + 31) / 32;
-      const unsigned grid = (unsigned)std::min<long>((n_tiles + 3) / 4, 8L * ctx->n_cu);
-      hipLaunchKernelGGL((cn_stem_mfma_kernel<XT>), dim3(grid), dim3(256), 0, s, ws.logmel, g.F, g.H[0], n_pos, ctx->stem_w, ctx->stem_b,
-                         ctx->stem_ln_w, ctx->stem_ln_b, wsx);
-    }
-#else
-    hipLaunchKernelGGL((cn_stem_kernel<1, XT>), dim3((unsigned)((n_pos + 63) / 64)), dim3(256), 0, s, ws.logmel, g.F, g.H[0],
-                       n_pos, ctx->stem_w, ctx->stem_b, ctx->stem_ln_w, ctx->stem_ln_b, wsx);
-#endif
+    const long n_tiles = (n_pos + 31) / 32;
+    const unsigned grid = (unsigned)std::min<long>((n_tiles + 3) / 4, 8L * ctx->n_cu);
+    hipLaunchKernelGGL((cn_stem_mfma_kernel<XT>), dim3(grid), dim3(256), 0, s, ws.logmel, g.F, g.H[0], n_pos, ctx->stem_w, ctx->stem_b,
+                       ctx->stem_ln_w, ctx->stem_ln_b, wsx);
     CN_LAUNCH_CHECK();
     if (taps) CN_TRY(tap_copy(taps->stem, wsx, (size_t)n_pos * 96, s));
   }
@@ -1131,33 +1020,25 @@ static int encode_impl(conette_ctx* ctx, const float* wave, int B, int L, float*
         }
       }
       if constexpr (CnIsH16<T>::value) if (!fused) {
-        // stages 0-2: register-chained fused MLP (mlp_rc2.h): the 4C hidden never leaves the registers; timed under PW1
+        // stages 0-2: fused MLP (mlp_rc2.h, register-chained; stage 2: mlp_rs16.h, role-split): the 4C hidden never leaves the
+        // registers / LDS; timed under PW1
         if (bw.mlp_stream != nullptr && C <= 384) {
           CnProfScope ps(ctx, CONETTE_PROF_PW1_GEMM, s);
           const T* wsm = (const T*)bw.mlp_stream;
           if (C == 96) CN_TRY((cn_launch_mlp_rc2_resident<96, 12, 1>(y, wsm, xc, (int)P, ctx->n_cu - ctx->enc_reserved_cus, s)));
           else if (C == 192) CN_TRY((cn_launch_mlp_rc2_ring<192, 8, CN_RC2_NCK(192), CN_RC2_NCK(192) == 2 ? 3 : 5>(y, wsm, xc, (int)P, ctx->n_cu - ctx->enc_reserved_cus, s)));
-#ifdef CN_NO_RS  // A/B builds only (tools/lab/ab.sh): round 2's chained kernel at stage 2
-          else CN_TRY((cn_launch_mlp_rc2_ring<384, 4, 1, 3>(y, wsm, xc, (int)P, ctx->n_cu - ctx->enc_reserved_cus, s)));
-#else
+          // C = 384: the role-split pipeline on 16x16x32 MFMAs (mlp_rs16.h; 125 us against 132 for the 32x32x16 form of rounds 3-4,
+          // profiles/r05_notes.md section 8); api.hip packed the stream for it.
           // (8 = the B waves -- GEMM2 + ring refill, the younger half of the block -- run at s_setprio 1: 143 against 148 us in the
           // lab with the fp16 residual stream, profiles/r05_notes.md; the MI355X guide's "static priority for the younger half")
-          // 16-bit residual stream: the same pipeline on 16x16x32 MFMAs (mlp_rs16.h; 125 against 132 us, profiles/r05_notes.md section 8);
-          // the stream was packed for the kernel that runs (api.hip)
-          else if constexpr (sizeof(XT) == 2 && CN_RS16) CN_TRY((cn_launch_mlp_rs16<384, 4, 3, CN_RS_PRIO>(y, wsm, xc, (int)P, ctx->n_cu - ctx->enc_reserved_cus, s)));
-          else CN_TRY((cn_launch_mlp_rs<384, 4, 3, CN_RS_PRIO>(y, wsm, xc, (int)P, ctx->n_cu - ctx->enc_reserved_cus, s)));
-#endif
+          else CN_TRY((cn_launch_mlp_rs16<384, 4, 3, 8>(y, wsm, xc, (int)P, ctx->n_cu - ctx->enc_reserved_cus, s)));
           fused = true;
         }
       }
       if (!fused) {
         {
           CnProfScope ps(ctx, CONETTE_PROF_PW1_GEMM, s);
-#ifdef CN_G2_NOACT  // timing experiment only (wrong results): how much of the epilogue is the activation?
-          constexpr int kAct = ACT_NONE;
-#else
           constexpr int kAct = CnGeluAct<T>::value;
-#endif
           EpiBiasAct<T, kAct> e1{bw.b1, hbuf, 4 * C, kAct};
           CN_TRY(cn_mm(y, C, (const T*)bw.w1, C, (int)P, 4 * C, C, e1, s));
         }

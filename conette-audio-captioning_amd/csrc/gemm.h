@@ -1,10 +1,9 @@
 // NT GEMM for gfx950 MFMA:  C[m][n] = sum_k A[m][k] * W[n][k]   (A: activations, W: nn.Linear weight)
 //
-// Used for the ConvNeXt pointwise 1x1 convs, the 2x2/2 downsample convs (as patch GEMMs), the
-// projection, and the decoder QKV / out / FFN / classifier GEMMs (north_star: MFMA only there).
+// Used in the fp32 parity mode (cn_mm, gemm2.h: the 16-bit and exact precisions run gemm2.h) for the ConvNeXt pointwise 1x1
+// convs, the 2x2/2 downsample convs (as patch GEMMs), the projection, and the decoder QKV / out / FFN / classifier GEMMs.
 //
-// * operand type T = bf16 (v_mfma_f32_16x16x32_bf16) or float (v_mfma_f32_16x16x4_f32, exact
-//   fp32 FMA chain -> the fp32 parity mode); accumulation always fp32.
+// * operand type T = float (v_mfma_f32_16x16x4_f32, exact fp32 FMA chain); accumulation fp32.
 // * "transposed" tile orientation: W rows feed the MFMA A operand and activation rows feed the
 //   B operand, so each lane ends up with 4 CONSECUTIVE n for one m -> one 8/16-byte store per
 //   lane in the epilogue instead of four scalar stores.
@@ -15,13 +14,9 @@
 #include "common.h"
 
 template <typename T> struct GemmTraits;
-template <> struct GemmTraits<bf16_t> {
-  static constexpr int ROW_BYTES = 64 + 16;
-  static constexpr int CPR = 4;  // 16-byte chunks per 32-element row
-};
 template <> struct GemmTraits<float> {
   static constexpr int ROW_BYTES = 128 + 16;
-  static constexpr int CPR = 8;
+  static constexpr int CPR = 8;  // 16-byte chunks per 32-element row
 };
 
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_GELU_FAST = 4, ACT_GELU_AS = 5 };
@@ -175,11 +170,9 @@ template <typename XT> struct EpiResidT {
 typedef EpiResidT<float> EpiResid;
 
 template <typename T> struct Frag8;
-template <> struct Frag8<bf16_t> { typedef bf16x8 type; };
 template <> struct Frag8<float> { struct type { f32x4 lo, hi; }; };
 
 template <typename T> __device__ __forceinline__ typename Frag8<T>::type cn_lds_frag(const char* p);
-template <> __device__ __forceinline__ bf16x8 cn_lds_frag<bf16_t>(const char* p) { return *(const bf16x8*)p; }
 template <> __device__ __forceinline__ Frag8<float>::type cn_lds_frag<float>(const char* p) {
   Frag8<float>::type f;
   f.lo = *(const f32x4*)p;
@@ -187,9 +180,6 @@ template <> __device__ __forceinline__ Frag8<float>::type cn_lds_frag<float>(con
   return f;
 }
 
-__device__ __forceinline__ f32x4 cn_mma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ f32x4 cn_mma(const Frag8<float>::type& a, const Frag8<float>::type& b, f32x4 c) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo[j], b.lo[j], c, 0, 0, 0);

@@ -446,7 +446,6 @@ static int cn_gemm2(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, i
     const bool n96 = (N % 96 == 0) && (N % 128 != 0);
     if (!k64) return cn_launch_gemm2_t<128, 128, 32, 2, Epi, 2, 2, OPK>(A, lda, W, ldw, M, N, K, splits, epi, stream);
     if (n96) return cn_launch_gemm2_t<128, 96, 64, 2, Epi, 2, 2, OPK>(A, lda, W, ldw, M, N, K, splits, epi, stream);
-#ifndef CN_G2_NO256
     // 256 x 256 tiles, 8 waves (2 x 4), one block per CU: a 128 x 128 tile asks the CU's load path for 512 bytes per MFMA
     // -- all of the ~64 B/clk it delivers when four SIMDs run MFMAs back to back -- this one for 256
     // A launch of several rounds over the chip takes 224-row tiles when that saves row-rounds (M = 13 888, N = 3072: 3 rounds
@@ -465,7 +464,6 @@ static int cn_gemm2(const bf16_t* A, int lda, const bf16_t* W, int ldw, int M, i
         return cn_launch_gemm2_t<224, 256, 64, 2, Epi, 2, 4, OPK>(A, lda, W, ldw, M, N, K, splits, epi, stream);
       return cn_launch_gemm2_t<256, 256, 64, 2, Epi, 2, 4, OPK>(A, lda, W, ldw, M, N, K, splits, epi, stream);
     }
-#endif
     return cn_launch_gemm2_t<128, 128, 64, 2, Epi, 2, 2, OPK>(A, lda, W, ldw, M, N, K, splits, epi, stream);
   }
   if (!k64) return cn_launch_gemm2_t<64, 64, 32, 2, Epi, 2, 2, OPK>(A, lda, W, ldw, M, N, K, splits, epi, stream);

@@ -39,45 +39,12 @@ template <int C, int NCK> struct Rc2Geom {
 // channels 16 (r >> 3) + 8 h + (r & 7): registers 0-7 and 8-15 are two runs of 8 consecutive channels.
 __host__ __device__ constexpr int cn_rc2_chan(int m) { return (m & 19) | ((m & 4) << 1) | ((m & 8) >> 1); }
 
-// GELU as x * sigmoid(x (a + b x^2 + c x^4)): minimax fit of the logit of the normal CDF on [-8, 8], max |error|
-// against the exact erf form 2.5e-5 (tanh form: 4.7e-4).  x^2 is clamped at 64, where the quartic would bend back.
-__device__ __forceinline__ float cn_gelu_sig2(float x) {
-  constexpr float L2E = 1.4426950408889634f;
-  const float x2 = fminf(x * x, 64.0f);
-  float p = fmaf(x2, 0.0007030350670982541f * L2E, -0.07401130190658815f * L2E);
-  p = fmaf(p, x2, -1.5950157568571721f * L2E);
-  const float e = __builtin_amdgcn_exp2f(x * p);
-  return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-// (cn_gelu_e1<DEG>: common.h -- the one-transcendental form of round 5)
-// The GELU of the fused MLP kernels.  Unless this is an A/B build of the sigmoid form, the packed W1 / b1 operands carry a factor
-// 1/2 (CN_MLP_XSCALE, applied by the packers below) and the accumulator of GEMM1 is x / 2.
-#if defined(CN_GELU_SIG2)
-#define CN_MLP_XSCALE 1.0f
-#else
+// The GELU of the fused MLP kernels: the one-transcendental form of round 5 (cn_gelu_e1_half, common.h), degree 5 for fp16
+// operands and 3 for bf16.  It takes x / 2: the packed W1 / b1 operands carry the factor 1/2 (CN_MLP_XSCALE, applied by the
+// packers below), so the accumulator of GEMM1 is x / 2.  (The two-transcendental sigmoid form of rounds 2-4: tools/lab/gelu_sig2.h.)
 #define CN_MLP_XSCALE 0.5f
-#endif
 template <typename HT> __device__ __forceinline__ float cn_gelu_mlp(float x) {
-#if defined(CN_GELU_SIG2)   // A/B builds: the two-transcendental sigmoid form of rounds 2-4
-  return cn_gelu_sig2(x);
-#elif defined(CN_GELU_E1_DEG)
-  return cn_gelu_e1_half<CN_GELU_E1_DEG>(x);
-#else
   return cn_gelu_e1_half<__is_same(HT, half_t) ? 5 : 3>(x);
-#endif
-}
-
-// two elements at once: v_pk_mul / v_pk_fma / v_pk_add carry both (the two min, exp2 and rcp stay scalar)
-__device__ __forceinline__ f32x2 cn_gelu_sig2_pk(f32x2 x) {
-  constexpr float L2E = 1.4426950408889634f;
-  f32x2 x2 = x * x;
-  x2 = f32x2{fminf(x2[0], 64.0f), fminf(x2[1], 64.0f)};
-  f32x2 p = x2 * (0.0007030350670982541f * L2E) + (-0.07401130190658815f * L2E);
-  p = p * x2 + (-1.5950157568571721f * L2E);
-  const f32x2 u = x * p;
-  const f32x2 d = f32x2{__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])} + 1.0f;
-  return x * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 
 // ---- packing (fp32 nn.Linear layouts -> fragment stream + aux) ------------------------------------------------------
@@ -131,11 +98,6 @@ static __global__ void pk_mlp_rc2(const float* __restrict__ W1, const float* __r
 // hidden chunks (of 32) per step: two at C = 192 (3-deep ring of 50 KB entries), one elsewhere
 #define CN_RC2_NCK(C) ((C) == 192 ? 2 : 1)
 
-// sched_group_barrier masks (LLVM AMDGPU IGroupLP)
-#define CN_SG_VALU 0x002
-#define CN_SG_MFMA 0x008
-#define CN_SG_DSR 0x100
-
 // Ring pieces go through cn_dma16_s (common.h: inline-asm LDS-DMA; the builtin cost a full lgkmcnt drain at every fifth
 // MFMA of the step loop).  (Lab: issuing piece q INSIDE the step, behind MFMA q by wave q % NW, only moved the ~70 cycles
 // a piece costs its wave from the top of the step into the step, MFMAs or not: 201 us against 189.  profiles/r02_notes.md)
@@ -144,7 +106,6 @@ template <int C, int NCK, typename HT = bf16_t, typename XT = float> struct Rc2W
   typedef Rc2Geom<C, NCK> G;
   typedef cn_h8<HT> hx8;
   static constexpr int KS1 = G::KS1, NT2 = G::NT2, F1 = G::F1, F2 = G::F2;
-  static constexpr int NV = 88;  // VALU instructions of the GELU + bf16 packing of 8 accumulator registers (approx.)
 
   static __device__ __forceinline__ hx8 frag(const char* wc, int f) { return *(const hx8*)(wc + f * 1024); }
   static __device__ __forceinline__ f32x16 mma(hx8 a, hx8 b, f32x16 c) { return cn_mma32(a, b, c); }
@@ -181,17 +142,8 @@ template <int C, int NCK, typename HT = bf16_t, typename XT = float> struct Rc2W
   }
   template <int Q, int I, int E>
   static __device__ __forceinline__ void gelu_slices(State& st) {  // (compile-time recursion: every index is a constant)
-#if defined(CN_RC2_GELU_PK) && defined(CN_GELU_SIG2)
-    if constexpr ((E & 1) == 0 && gelu_at(I, E) == Q) {  // pairs (E, E + 1) ride together behind MFMA gelu_at(I, E)
-      const f32x2 r = cn_gelu_sig2_pk(f32x2{st.X[I][E], st.X[I][E + 1]});
-      st.g[I][E] = r[0];
-      st.g[I][E + 1] = r[1];
-    }
-    if constexpr (gelu_at(I, E & ~1) == Q) {
-#else
     if constexpr (gelu_at(I, E) == Q) {
       st.g[I][E] = cn_gelu_mlp<HT>(st.X[I][E]);
-#endif
       if constexpr ((E & 7) == 7) {
         constexpr int o = E - 7;
         st.H[I][E >> 3] = cn_sat8<HT>(cn_pack8<HT>(st.g[I][o], st.g[I][o + 1], st.g[I][o + 2], st.g[I][o + 3],

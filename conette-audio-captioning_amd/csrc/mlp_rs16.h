@@ -1,8 +1,23 @@
-// Role-split fused ConvNeXt MLP on v_mfma_f32_16x16x32 (16-bit operands, 16-bit residual stream) -- the kernel of mlp_rs.h with
-// every 32 x 32 x 16 product replaced by four 16 x 16 x 32 ones.  Same pipeline (A wave: GEMM1 + GELU, B wave: GEMM2, one hidden
-// chunk of 32 units per step, ring of packed entries, two barriers per step), same ring protocol and tile-boundary
-// software pipelining; what changes is the tiling inside a step:
+// Role-split fused ConvNeXt MLP on v_mfma_f32_16x16x32 (16-bit operands HT = bf16_t | half_t, 16-bit residual stream XT) -- the
+// stage-2 (C = 384) pointwise kernel, third generation (mlp_rc2.h is the second):
 //
+//     x[m][:] += scale * ( W2 . gelu( W1 . y[m][:] + b1 ) + b2 )          (convnext.py:66-74)
+//
+// The register-chained kernel runs GEMM1 -> GELU -> GEMM2 of a hidden chunk inside ONE wave: at C = 384 that wave needs
+// y (96 registers) + O (192) and is alone on its SIMD, so the chain's dependencies are paid in full (MFMA pipe 0.36 busy).
+// Here the chain is cut across TWO waves that share a SIMD and a 32-position tile:
+//   * an A wave holds y and computes X = W1c . y^T + b1, runs the GELU and hands the converted chunk (32 pos x 32 hidden,
+//     16-bit, already in the operand order of GEMM2: the accumulator layout IS the operand layout of a product that sums
+//     over the hidden units) to its partner through 2 KB of LDS;
+//   * a B wave holds O (starts from the residual) and only runs O^T += W2c' . G^T.
+// Software pipeline over the hidden chunks of a tile (one step = one chunk of 32 units, one ring entry):
+//     step g:   A: GEMM1(g) interleaved with the GELU of X(g-1), G(g-1) -> LDS      B: GEMM2(g-2) from G(g-2)
+// so no wave ever waits for its own MFMA results: A's VALU work belongs to the previous chunk, B is a plain MFMA loop,
+// and the two waves of a SIMD fill each other's issue gaps.  Registers: A = y + 2 X + fragments, B = O + fragments;
+// both <= 256 at C = 384 -> 2 waves per SIMD where the chained kernel had one.
+//
+// Tiling inside a step (four 16 x 16 x 32 products where the first role-split kernel -- tools/lab/mlp_rs.h, round 3 -- ran one
+// 32 x 32 x 16):
 //   A:  X[mbh][nb] (16 hidden x 16 positions, 4 registers) += W1 fragment (ks, mbh) . y fragment (nb, ks), ks < C / 32;
 //       one LDS read feeds two MFMAs (nb = 0, 1); the accumulators START from b1 (an fp32 fragment of the entry: no bias
 //       k-step, no hi + lo split).  Accumulator lane (n, q) register i = hidden 16 mbh + 4 q + i of position 16 nb + n, so a
@@ -10,21 +25,38 @@
 //       and written to the hand-over buffer at lane * 16, read back by the B wave at lane * 16: no lane movement.
 //   B:  O[mb][nb] (16 channels x 16 positions) += W2 fragment (mb) . G fragment (nb); row 4 q + i of m-block mb is channel
 //       32 (mb >> 1) + 8 q + 4 (mb & 1) + i, so the m-block pair (2 p, 2 p + 1) gives a lane eight CONSECUTIVE channels of
-//       its position: the residual moves as one 16-byte piece per (pair, nb) -- 24 loads + 24 stores per tile row set,
-//       as in mlp_rs.h.
+//       its position: the residual moves as one 16-byte piece per (pair, nb) -- 24 loads + 24 stores per tile row set.
 //
-// Ring entry e (pk_mlp_rs16): [W1 fragments (ks, mbh) at 2 ks + mbh: C / 16][b1 fragments (mbh), fp32: 2]
-// [W2' fragments of chunk (e - 2) mod NCH, mb < C / 16], 1 KB each: C / 8 + 2 KB; then bb = s b2 (fp32, C).
+// Ring entry e (1 KB fragments, packed by pk_mlp_rs16): [W1 fragments (ks, mbh) at 2 ks + mbh: C / 16][b1 fragments (mbh),
+// fp32: 2][W2' fragments of chunk (e - 2) mod NCH, mb < C / 16]: C / 8 + 2 KB, NCH = C / 8 entries; then bb = s b2 (fp32, C).
+// The W2 part of entry e belongs to the chunk B works on while A works on chunk e, so an entry is consumed whole by one
+// step and the ring protocol is the chained kernel's: entry g + NST - 1 is requested at the start of step g.
 //
-// Why: MI355X guide -- the 16 x 16 x 32 instruction is the power-cheaper shape (1.12-1.15x the delivered rate of the
-// 32 x 32 x 16 loop when the clock is what binds); the skeleton of mlp_rs.h runs at 0.44 of the matrix peak for exactly
-// that reason (profiles/r05_notes.md section 3).
+// LDS: NST x (C/8 + 2) KB ring + NP x 2 KB hand-over buffers (single-buffered: two barriers per step -- the first
+// publishes entry g and G(g-1), B takes G(g-1) into registers, the second lets A overwrite it) + bb (C fp32).
+//
+// The ring refill (1 KB LDS-DMA pieces) is issued by the B waves INSIDE their MFMA loop: B has no VALU work, so a piece
+// fits the gap behind one of its MFMAs while the partner's MFMA runs (issued between the barriers instead, with every wave
+// taking a share, the refill cost 60 us of a 209 us launch at C = 384; inside B's loop 15).
+// Tile boundaries are software-pipelined into the steps around them:
+//   * A re-loads a y fragment of the NEXT tile in place, right behind the last MFMA of the tile that reads it (the first
+//     step of the next tile meets them one step later);
+//   * B runs its MFMAs m-block pair by pair, so that in a tile's last step the store of a pair's channel run and the load
+//     of the next position tile's residual follow the pair's last MFMA, one pair behind.  The loaded halves wait in
+//     registers that the stored run has just freed and are converted in the FIRST step of the next position tile, right
+//     before the first MFMA of their pair (a conversion at the load would wait for HBM in the middle of the step).
+//   Both are UNCONDITIONAL instruction streams (rows outside the tensor are masked per lane; a pair without a next tile
+//   re-loads rows it never uses): a branch around them, or a run-time choice between two instantiations of the step, made
+//   the register allocator give O different registers on the two paths and shuffle all 192 of them through scratch at the
+//   join.
+//
+// Why 16 x 16 x 32: MI355X guide -- it is the power-cheaper shape (1.12-1.15x the delivered rate of the 32 x 32 x 16 loop
+// when the clock is what binds); the 32 x 32 x 16 skeleton ran at 0.44 of the matrix peak for exactly that reason
+// (profiles/r05_notes.md section 3).
 #pragma once
-#include "mlp_rs.h"
+#include <type_traits>
 
-#ifndef CN_RS16
-#define CN_RS16 1  // 0 (A/B builds): stage 2 of the bf16 / f16 precisions on mlp_rs.h as in round 4
-#endif
+#include "mlp_rc2.h"
 
 template <int C> struct Rs16Geom {
   static constexpr int KS = C / 32;    // k-steps of GEMM1
@@ -71,12 +103,12 @@ static __global__ void pk_mlp_rs16(const float* __restrict__ W1, const float* __
   for (int i = 0; i < 8; ++i) o[i] = (HT)v[i];
 }
 
-// ABL as in mlp_rs.h (1 no ring refill, 2 GELU replaced by a copy, 4 no residual / y traffic at tile boundaries, 8 / 16 priority)
+// ABL (kernel lab only, wrong results unless 0 / 8 / 16): 1 = no ring refill after the prologue, 2 = GELU replaced by a copy,
+// 4 = no residual / y traffic at tile boundaries; 8 / 16 = static wave priority for the B / the A role
 template <int C, int NP, int ABL = 0, typename HT = bf16_t, typename XT = half_t> struct Rs16Wave {
-  static_assert(sizeof(XT) == 2, "16-bit residual stream only (the fp32 stream keeps mlp_rs.h)");
+  static_assert(sizeof(XT) == 2, "16-bit residual stream only");
   typedef Rs16Geom<C> G;
   typedef cn_h8<HT> hx8;
-  typedef typename RsWave<C, NP, ABL, HT, XT>::Dma Dma;
   static constexpr int KS = G::KS, NMB = G::NMB, NPR = G::NPR, F1 = G::F1, F2 = G::F2, FR = G::FR;
   static constexpr int NQ1 = 4 * KS, NQ2 = 2 * NMB;  // MFMAs of an A / B step
 #ifndef CN_RS16_PRE_A
@@ -154,6 +186,13 @@ template <int C, int NP, int ABL = 0, typename HT = bf16_t, typename XT = half_t
 
   // ---- B ------------------------------------------------------------------------------------------------------------------
   // MFMA Q = 2 mb + nb reads fragment mb.  raw[p][nb]: the eight residual halves of channels 32 p + 8 q .. + 8 at position 16 nb + n.
+  struct Dma {         // one ring entry's refill, as this B wave sees it
+    const char* src;   // entry to fetch (wave-uniform)
+    unsigned dst;      // LDS byte address of its slot
+    unsigned voff;     // lane * 16
+    int first;         // this wave's first piece; the others follow at stride NP
+    int n_pieces;      // pieces of the entry (0: nothing to issue)
+  };
   template <int I>
   static __device__ __forceinline__ void dma_piece(const Dma& d) {
     const int piece = d.first + I * NP;
@@ -184,7 +223,10 @@ template <int C, int NP, int ABL = 0, typename HT = bf16_t, typename XT = half_t
     *(cn_h8<XT>*)(xr + 32 * p) = cn_pack8<XT>(o0, o1, o2, o3, o4, o5, o6, o7);
   }
   // xrow / xnext: row pointers of nb = 0 and nb = 1 with the lane's channel offset applied (two pointers each: a pair without a
-  // next tile re-reads ONE row for both).  FIRST / LAST and the unconditional instruction streams: see mlp_rs.h b_mstep.
+  // next tile re-reads ONE row for both).
+  // LAST: the tile's last chunk -- one pair behind the MFMAs, the pair's channel run (+ bb) is stored and the residual of the
+  // wave's next position tile is loaded (raw[p]).  FIRST: the tile's first chunk -- raw[p] becomes O right before the first
+  // MFMA of pair p.  Both are unconditional instruction streams (file header).
   struct Rows {
     XT* x[2];
     const XT* next[2];
@@ -225,7 +267,7 @@ template <int C, int NP, int ABL = 0, typename HT = bf16_t, typename XT = half_t
       }
     }
   }
-  static __device__ __forceinline__ void issue_all(const Dma& d) {
+  static __device__ __forceinline__ void issue_all(const Dma& d) {  // a step without a tile still owes the refill
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
       const int piece = d.first + i * NP;
@@ -234,7 +276,8 @@ template <int C, int NP, int ABL = 0, typename HT = bf16_t, typename XT = half_t
   }
 };
 
-// Launch geometry and roles as cn_mlp_rs_kernel (mlp_rs.h): NP pairs per block, waves [0, NP) are the A roles.
+// NP pairs per block (2 NP waves: waves [0, NP) are the A roles, [NP, 2 NP) the B roles: with waves dealt round-robin over the
+// four SIMDs a pair shares its SIMD when NP is a multiple of 4); pair p owns tiles t_lo + p + it * NP of the block's range.
 template <int C, int NP, int NST, int ABL = 0, typename HT = bf16_t, typename XT = half_t>
 __global__ __launch_bounds__(2 * NP * 64) void cn_mlp_rs16_kernel(const HT* __restrict__ Y, const HT* __restrict__ WS,
                                                                   XT* __restrict__ X, int M) {
@@ -269,9 +312,11 @@ __global__ __launch_bounds__(2 * NP * 64) void cn_mlp_rs16_kernel(const HT* __re
   for (int g = 0; g < NST - 1; ++g) RW::issue_all(entry(g));
   const char* wl = smem + lane * 16;
   char* gl = gbuf + pair * 2048 + lane * 16;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // bb is in LDS before the first barrier
 
-  if constexpr ((ABL & 24) != 0) {
+  // Both roles run max_it * NCH + 2 steps of two barriers each; their loops have NO run-time choice between step variants
+  // (file header): the last step of a tile is peeled behind the loop over the others.
+  if constexpr ((ABL & 24) != 0) {  // static wave priority for one of the roles (8: B, 16: A)
     if (role_b == ((ABL & 8) != 0)) __builtin_amdgcn_s_setprio(1);
   }
   if (!role_b) {
@@ -283,14 +328,14 @@ __global__ __launch_bounds__(2 * NP * 64) void cn_mlp_rs16_kernel(const HT* __re
 #pragma unroll
       for (int b = 0; b < 2; ++b) Xa[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}, Xb[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int yoff = (lane & 15) * C + 8 * (lane >> 4);
-    const int tile0 = t_lo + pair < t_hi ? t_lo + pair : t_lo;
+    const int tile0 = t_lo + pair < t_hi ? t_lo + pair : t_lo;  // (a pair without a tile multiplies rows nobody stores)
     RW::load_y(Y, tile0 * 32, lane, fy);
     int g = 0;
-    auto step2 = [&](auto reload_tag, const HT* ynext) {
+    auto step2 = [&](auto reload_tag, const HT* ynext) {  // two steps: the roles of the two X accumulators swap
       constexpr bool RELOAD = decltype(reload_tag)::value;
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_s_barrier();
-      RW::template a_step<false>(wl + (g % NST) * SB, fy, Xb, Xa, gl, ynext);
+      RW::template a_step<false>(wl + (g % NST) * SB, fy, Xb, Xa, gl, ynext);  // GEMM1(g) -> Xa, GELU of Xb (chunk g - 1) -> G
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       ++g;
       __builtin_amdgcn_s_barrier();
@@ -302,12 +347,14 @@ __global__ __launch_bounds__(2 * NP * 64) void cn_mlp_rs16_kernel(const HT* __re
     for (int it = 0; it < max_it; ++it) {
       const int tile = t_lo + pair + it * NP;
       const bool has_next = tile + NP < t_hi && !(ABL & 4);
-      // (no next tile: every lane re-reads rows 0 and 16 of the pair's first tile, not a whole tile it never uses)
+      // No next tile: the re-load stays an unconditional instruction stream but every lane reads rows 0 and 16 of the pair's
+      // first tile -- two 768-byte rows instead of a whole 24 KB tile.  (Round 3 re-read the first tile here: with two tiles
+      // per pair and launch that was + 50 % of the y and residual reads, the "1.39x FETCH_SIZE" of VERDICT r03.)
       const HT* ynext = has_next ? Y + (size_t)(tile + NP) * 32 * C + yoff : Y + (size_t)tile0 * 32 * C + 8 * (lane >> 4);
       for (int j = 0; j < NCH - 2; j += 2) step2(std::false_type{}, ynext);
-      step2(std::true_type{}, ynext);
+      step2(std::true_type{}, ynext);  // the tile's last two steps: the second re-loads y in place
     }
-    step2(std::false_type{}, Y);
+    step2(std::false_type{}, Y);  // trailing: the GELU of the last chunk (B is two chunks behind)
   } else {
     // ================================================= B ==============================================================
     f32x4 O[G::NMB][2];
@@ -324,9 +371,13 @@ __global__ __launch_bounds__(2 * NP * 64) void cn_mlp_rs16_kernel(const HT* __re
     }
     int g = 0;
     constexpr int IO_H = G::NPR;  // 16-byte operations per nb half of a tile boundary (loads; as many stores)
+    // the last step in which this wave ran a tile boundary, and the vector-memory operations it really issued there
     int io_step = -1000, io_n = 0;
     hx8 H[2];
-    auto head = [&]() {
+    auto head = [&]() {  // ring wait, first barrier, G(g - 2) -> registers, second barrier
+      // Own pieces of the entry about to be consumed have landed.  They were issued in step g - (NST - 1); younger than them
+      // (the counter retires in order) are the pieces of NST - 2 later entries and, if a tile boundary fell strictly
+      // between, its stores and loads.
       cn_vm_wait((NST - 2) * n_mine + ((io_step > g - (NST - 1) && io_step < g) ? io_n : 0));
       __builtin_amdgcn_s_barrier();
       H[0] = *(const hx8*)gl;
@@ -334,7 +385,7 @@ __global__ __launch_bounds__(2 * NP * 64) void cn_mlp_rs16_kernel(const HT* __re
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     };
-    for (int i = 0; i < 2; ++i, ++g) {
+    for (int i = 0; i < 2; ++i, ++g) {  // B runs two chunks behind A: nothing to multiply yet, the refill is still owed
       head();
       RW::issue_all(entry(g + NST - 1));
     }
@@ -366,7 +417,7 @@ __global__ __launch_bounds__(2 * NP * 64) void cn_mlp_rs16_kernel(const HT* __re
       ++g;
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the ring was filled NST - 1 entries past the end
 }
 
 template <int C, int NP, int NST, int ABL = 0, typename HT, typename XT>

@@ -17,7 +17,7 @@ Rounding points (conette-audio-captioning_amd/csrc):
       the depthwise convolution reads those fp16 values as exact operands and -- since the second half of round 5, when it adds two taps
       per v_dot2_f32_f16 -- its 7 x 7 weights as fp16 operands too (``res16`` of dwconv.weight: 2^-12 relative); products exact, sums fp32.
 The GPU evaluates GELU through approximations that are exact to <= 5.5e-5 absolute (bf16) / 8.6e-7 (fp16) in the fused MLP
-(common.h cn_gelu_e1) and 1.5e-7 elsewhere (A&S 7.1.26, common.h); the oracle uses the exact erf form, so a handful of hidden
+(common.h cn_gelu_e1_half) and 1.5e-7 elsewhere (A&S 7.1.26, common.h); the oracle uses the exact erf form, so a handful of hidden
 values per million round to the neighbouring bf16.
 """
 from __future__ import annotations

@@ -14,7 +14,7 @@ the kernel's quantisation points, fp32 accumulation and fp32 everything else:
 
 e4m3 is the OCP "fn" format (max 448, no infinities), round to nearest even -- torch.float8_e4m3fn on the CPU.  With 3
 mantissa bits a value that lands on the other side of a rounding boundary moves by 1/8 of its magnitude, so the GELU is
-restated in the kernel's own form -- x sigmoid(x (a + b x^2 + c x^4)), mlp_rc2.h cn_gelu_sig2: 2.5e-5 from erf, which
+restated in the kernel's own form -- x sigmoid(x (a + b x^2 + c x^4)), tools/lab/gelu_sig2.h cn_gelu_sig2: 2.5e-5 from erf, which
 would flip about one hidden value per position -- and what is left are the y values whose LayerNorm (computed to ~1e-6 by
 both sides) straddles a boundary: ~1e-3 of the positions carry one flipped operand, and the test budgets for them.
 """
@@ -36,7 +36,7 @@ def e4m3(t: Tensor) -> Tensor:
 
 
 def gelu_sig2(x: Tensor) -> Tensor:
-    """csrc/mlp_rc2.h cn_gelu_sig2: x * sigmoid(x (a + b x^2 + c x^4)), x^2 clamped at 64 (minimax fit of the normal CDF's
+    """tools/lab/gelu_sig2.h cn_gelu_sig2: x * sigmoid(x (a + b x^2 + c x^4)), x^2 clamped at 64 (minimax fit of the normal CDF's
     logit on [-8, 8]; max |error| against the erf form 2.5e-5)."""
     x2 = (x * x).clamp(max=64.0)
     p = (0.0007030350670982541 * x2 - 0.07401130190658815) * x2 - 1.5950157568571721

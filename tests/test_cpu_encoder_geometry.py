@@ -28,7 +28,7 @@ def test_depthwise_tiles_match_the_sources():
     assert _one(r"#define CN_DW192_TH (\d+)", enc) == E.CN_DW192_TH
     assert _one(r"#define CN_FW_TH (\d+)", enc) == E.CN_FW_TH
     assert _one(r"launch_dwconv_fw<T, XT, 768, 7, (\d+)>", enc) == E.FW768_TH
-    # the fp32 stream's rows per tile at stages 0 / 1 (dwconv_dispatch: "(sizeof(XT) == 2 && CN_DW_DOT2) ? CN_DW96_TH : 8")
+    # the fp32 stream's rows per tile at stages 0 / 1 (dwconv_dispatch: "sizeof(XT) == 2 ? CN_DW96_TH : 8")
     assert _one(r"\? CN_DW96_TH : (\d+)>", enc) == E.F32_DW_TH
     assert _one(r"\? CN_DW192_TH : (\d+)>", enc) == E.F32_DW_TH
     # stage 2 / 3 run the full-width kernels only at the widths of the encoder's geometry

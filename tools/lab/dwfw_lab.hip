@@ -8,7 +8,6 @@
 #ifndef FW_ABL
 #define FW_ABL 0
 #endif
-#define CN_DW_DOT2 1
 __device__ int g_cn_nonfinite;
 __device__ __forceinline__ void cn_watch_stat(float v) {
   if (!(__builtin_fabsf(v) <= 3.0e38f)) atomicAdd(&g_cn_nonfinite, 1);

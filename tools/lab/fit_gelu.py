@@ -1,4 +1,4 @@
-"""Minimax fit of the one-transcendental GELU of common.h cn_gelu_e1: gelu(x) = max(x, 0) - a 2^P(a), a = |x| (scipy; development aid)."""
+"""Minimax fit of the one-transcendental GELU of common.h cn_gelu_e1_half: gelu(x) = max(x, 0) - a 2^P(a), a = |x| (scipy; development aid)."""
 import numpy as np
 from scipy.special import erfc
 from scipy.optimize import least_squares

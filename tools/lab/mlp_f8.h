@@ -23,6 +23,7 @@
 // sc[C], 1/sc[C], bb[C] = ls b2, 1/s1.
 #pragma once
 #include "mlp_rc2.h"
+#include "gelu_sig2.h"
 
 template <int C> struct Rc2F8Geom {
   static constexpr int KS1 = C / 16, NT2 = C / 32, NSTEP = C / 8;

@@ -1,5 +1,5 @@
 // Kernel lab for the fused ConvNeXt MLP kernels (development aid, not part of the product library):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCN_RC2_GELU_PK -I conette-audio-captioning_amd/csrc -I tools/lab tools/lab/mlp_lab.hip -o tools/lab/mlp_lab
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I conette-audio-captioning_amd/csrc -I tools/lab tools/lab/mlp_lab.hip -o tools/lab/mlp_lab
 //   tools/lab/mlp_lab [C] [batch] [iters]
 // Checks every variant against a naive bf16-operand reference kernel on a small M (full tensors), then times it on
 // the benchmark shape (batch x positions-per-clip rows) with HIP events, interleaved rounds.
@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "mlp_rc2.h"
+#include "gelu_sig2.h"
 #include "mlp_f8.h"
 #include "mlp_rs.h"
 #include "mlp_rs16.h"

@@ -4,6 +4,7 @@
 // against 181 us (same box).  profiles/r02_notes.md.  Include after mlp_rc2.h.
 #pragma once
 #include "mlp_rc2.h"
+#include "gelu_sig2.h"
 
 // skew (NCK = 1 only): a step's entry is [W1 of chunk st | W2 k-half 1 of chunk st - 1 (cyclic) | W2 k-half 0 of chunk st]:
 // the second half of a chunk's GEMM2 runs one step late, under it the first half of the NEXT chunk's GELU (Rc2Skew).
