@@ -130,6 +130,27 @@ class BaselinePLM:
             raise ValueError(f"expected frame embeddings of shape (bsize, [1,] time, 768), found {tuple(audio.shape)}")
         return {"frame_embs": audio, "frame_embs_lens": torch.as_tensor(audio_shape)[:, 1].to(torch.int32)}
 
+    def score_captions(self, batch: Dict[str, Any], captions: Tensor) -> Dict[str, Tensor]:
+        """``CoNeTTEModel.score_captions`` over precomputed frame embeddings (``batch`` = {"audio", "audio_shape"}): captions
+        (B, L) or (B, n_caps, L) full ids -- <bos>, words, <eos>, pad_id; no task token in this family -- -> {"lprobs",
+        "sum_lprobs", "n_tokens", "losses", "loss"}: the per-caption CrossEntropyLossMean of the forcing logits
+        (nn/loss/ce_mean.py:30-34) without the logits."""
+        from . import scoring
+        enc = self.encode_audio(batch["audio"], batch["audio_shape"])
+        captions = torch.as_tensor(captions)
+        if captions.is_floating_point() or captions.ndim not in (2, 3):
+            raise ValueError("captions must be an integer tensor of shape (bsize, caps_size) or (bsize, n_caps, caps_size).")
+        caps3 = captions[:, None] if captions.ndim == 2 else captions
+        b, n_caps, size = (int(v) for v in caps3.shape)
+        if b != enc["frame_embs"].shape[0]:
+            raise ValueError(f"Invalid number of captions {b} for {enc['frame_embs'].shape[0]} audio clips.")
+        caps_in, targets = scoring.split_captions(caps3.reshape(b * n_caps, size), self.pad_id)
+        res = self.engine.score(enc["frame_embs"], enc["frame_embs_lens"], caps_in, targets, caps_per_audio=n_caps)
+        sums, cnt = res["sum_lprobs"].reshape(b, n_caps), res["n_tokens"].reshape(b, n_caps)
+        losses = scoring.losses_from(sums, cnt)
+        return {"lprobs": res["tok_lprobs"].reshape(b, n_caps, size - 1), "sum_lprobs": sums, "n_tokens": cnt,
+                "losses": losses, "loss": losses.mean()}
+
     def decode_audio(self, encoder_outs: Dict[str, Tensor], decode_method: str, **kwargs) -> Any:
         """baseline.py:339-401: "forcing" -> logits (B, vocab, cap_len); "greedy" -> the masked logits of every step
         (B, vocab, pred_size) (greedy.py:17-131); "generate" -> (preds, lprobs, mult_preds, mult_lprobs) (beam.py:22-227)."""

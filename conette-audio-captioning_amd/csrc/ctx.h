@@ -111,6 +111,7 @@ struct conette_ctx {
   int n_cu;  // compute units of the device the context lives on (persistent-kernel grids)
   int enc_reserved_cus;  // CONETTE_OPT_ENCODE_RESERVED_CUS
   int forcing_stepwise;  // CONETTE_OPT_FORCING_STEPWISE
+  int score_vsplit;      // CONETTE_OPT_SCORE_VSPLIT (0: automatic)
   // arena
   char* arena;
   size_t arena_bytes;

@@ -17,6 +17,7 @@
 
 #include "gemm2.h"
 #include "dec_ffn.h"
+#include "dec_score.h"
 
 #define CN_MAX_BEAM 16  // beams 1..8: the register-resident step kernel; 9..16 (BaselinePLM's default is 10, baseline.py:47): the generic one
 #define CN_MAX_PRED 64
@@ -819,7 +820,8 @@ struct DecWs {
   size_t total;
 };
 
-static DecWs dec_ws(const conette_ctx* ctx, int B, int Ta, int beam, int maxp, char* base) {
+// `lean` (conette_score): no logits, no KV cache -- the one-pass layer loop uses neither, and scoring must not hold an (R, V) array
+static DecWs dec_ws(const conette_ctx* ctx, int B, int Ta, int beam, int maxp, char* base, bool lean = false) {
   const size_t es = ctx->esize;
   const int d = ctx->cfg.d_model, NL = ctx->cfg.n_layers, R = B * beam;
   DecWs w;
@@ -842,9 +844,9 @@ static DecWs dec_ws(const conette_ctx* ctx, int B, int Ta, int beam, int maxp, c
   w.tmp = (float*)take((size_t)R * d * 4);
   w.slabs = (float*)take((size_t)FF2_SPLITS * R * d * 4);
   w.ffh = take((size_t)R * ctx->cfg.d_ff * es);
-  w.logits = (float*)take((size_t)R * w.ldv * 4);
-  w.kc = take((size_t)NL * maxp * R * d * es);
-  w.vc = take((size_t)NL * maxp * R * d * es);
+  w.logits = (float*)take(lean ? 0 : (size_t)R * w.ldv * 4);
+  w.kc = take(lean ? 0 : (size_t)NL * maxp * R * d * es);
+  w.vc = take(lean ? 0 : (size_t)NL * maxp * R * d * es);
   w.n_active = (int*)take((size_t)B * 4);
   w.live = (int*)take((size_t)(CN_MAX_PRED + 2) * 4);
   w.slot = (int*)take((size_t)R * 4);
@@ -1234,6 +1236,14 @@ extern "C" int conette_set_option(conette_ctx* ctx, int32_t option, int32_t valu
     ctx->forcing_stepwise = value ? 1 : 0;
     return CN_OK;
   }
+  if (option == CONETTE_OPT_SCORE_VSPLIT) {
+    if (value < 0) {
+      cn_set_error("set_option: score vocabulary split %d < 0", value);
+      return CN_ERR_ARG;
+    }
+    ctx->score_vsplit = value;
+    return CN_OK;
+  }
   if (option == CONETTE_OPT_ENCODE_RESERVED_CUS) {
     if (value < 0 || value > ctx->n_cu / 2) {
       cn_set_error("set_option: reserved CUs %d outside 0 .. %d", value, ctx->n_cu / 2);
@@ -1413,6 +1423,9 @@ extern "C" int32_t conette_decode_graph_nodes(const conette_ctx* ctx) {
 // kernels of the step path with M = B * cap_len), the cross-attention kernel is reused with "beam" = cap_len, and the
 // self-attention reads the K / V of the clip's earlier positions from this pass's own QKV output -- at cache precision
 // (rounded to the operand type exactly as the step path stores and re-reads them), masked to valid (non-pad) keys <= t.
+// conette_score runs the same pass over `cpa` captions per clip (rows r = (clip * cpa + caption) * cap_len + position; the
+// projection and the cross-attention K / V once per CLIP, the cross-attention's "beam" = cpa * cap_len) and ends in the fused
+// classifier + log-soft-max + gather of dec_score.h instead of the classifier GEMM.
 template <typename T>
 __global__ __launch_bounds__(256) void cn_embed_caps_kernel(const int32_t* __restrict__ caps, const float* __restrict__ emb,
                                                             const float* __restrict__ pe, int cap_len, int R, float scale,
@@ -1465,12 +1478,19 @@ __global__ __launch_bounds__(256) void cn_self_attn_causal_kernel(const float* _
   cn_store4(out + (size_t)r * 256 + 4 * lane, acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
 }
 
+struct CnScoreOut {  // conette_score's tail of the pass
+  const int32_t* targets;
+  float* tok_lprobs;  // may be null
+  float* sum_lprobs;
+  int32_t* n_tokens;
+};
 template <typename T>
 static int forcing_prefill_impl(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* caps,
-                                int B, int Ta, int cap_len, float* logits, char* wsp, hipStream_t s) {
+                                int B, int Ta, int cpa, int cap_len, float* logits, const CnScoreOut* score, char* wsp,
+                                hipStream_t s) {
   const conette_config& cfg = ctx->cfg;
-  const int d = cfg.d_model, NL = cfg.n_layers, R = B * cap_len, V = cfg.vocab_size, dff = cfg.d_ff;
-  DecWs w = dec_ws(ctx, B, Ta, cap_len, 1, wsp);  // rows = B * cap_len ("beam" = cap_len, one step)
+  const int d = cfg.d_model, NL = cfg.n_layers, R = B * cpa * cap_len, V = cfg.vocab_size, dff = cfg.d_ff;
+  DecWs w = dec_ws(ctx, B, Ta, cpa * cap_len, 1, wsp, score != nullptr);  // rows = B * cpa * cap_len ("beam" = cpa * cap_len, one step)
   T* fe_t = (T*)w.fe_t;
   T* mem = (T*)w.mem;
   T* kvc = (T*)w.kvc;
@@ -1523,7 +1543,7 @@ static int forcing_prefill_impl(conette_ctx* ctx, const float* frame_embs, const
     {
       CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
       hipLaunchKernelGGL((cn_cross_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, kvc, kv_ld, l * 2 * d, frame_lens, R,
-                         cap_len, Ta, scale, attn_t);
+                         cpa * cap_len, Ta, scale, attn_t);
       CN_LAUNCH_CHECK();
     }
     {
@@ -1549,6 +1569,11 @@ static int forcing_prefill_impl(conette_ctx* ctx, const float* frame_embs, const
     CN_LAUNCH_CHECK();
   }
   CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+  if (score) {  // no logits: every row's log-probability of its target, summed per caption (dec_score.h)
+    const int S = cn_score_slabs(R, V, ctx->n_cu, ctx->score_vsplit);
+    return cn_score_launch<T>(xt, (const T*)ctx->cls_w, ctx->cls_b, score->targets, B * cpa, cap_len, V, S, cfg.pad_id,
+                              (float*)(wsp + w.total), score->tok_lprobs, score->sum_lprobs, score->n_tokens, s);
+  }
   EpiBiasAct<float, ACT_NONE> ec{ctx->cls_b, logits, V, ACT_NONE};  // (B, cap_len, V) written in place
   CN_TRY(cn_mm(xt, d, (const T*)ctx->cls_w, d, R, V, d, ec, s));
   return CN_OK;
@@ -1587,8 +1612,8 @@ extern "C" int conette_forcing(conette_ctx* ctx, const float* frame_embs, const 
   }
   hipStream_t s = (hipStream_t)stream;
   if (!ctx->forcing_stepwise) {  // default: one causal pass over all caption positions
-    CN_BY_PRECISION(ctx, forcing_prefill_impl<OT>(ctx, frame_embs, frame_lens, caps_in, batch, t_audio, cap_len, logits,
-                                          (char*)workspace, s));
+    CN_BY_PRECISION(ctx, forcing_prefill_impl<OT>(ctx, frame_embs, frame_lens, caps_in, batch, t_audio, 1, cap_len, logits,
+                                          nullptr, (char*)workspace, s));
   }
   // CONETTE_OPT_FORCING_STEPWISE: the KV-cached step kernels fed with the caption (cross-check of the pass above)
   // outputs of the search bookkeeping that a forced pass does not produce: parked in the workspace tail
@@ -1602,6 +1627,51 @@ extern "C" int conette_forcing(conette_ctx* ctx, const float* frame_embs, const 
   CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, frame_embs, frame_lens, caps_in, nullptr, batch, t_audio, 1, 0, cap_len, mult_preds,
                                mult_lprobs, mult_preds, mult_lprobs, sizes, nullptr, nullptr, nullptr, (char*)workspace, s,
                                caps_in, logits));
+}
+
+extern "C" size_t conette_score_workspace_bytes(const conette_ctx* ctx, int32_t n_audio, int32_t t_audio,
+                                                int32_t caps_per_audio, int32_t cap_len) {
+  if (!ctx || n_audio <= 0 || t_audio <= 0 || caps_per_audio <= 0 || cap_len <= 0) return 0;
+  const long rows = (long)n_audio * caps_per_audio * cap_len;
+  if (rows > 0x7fffffffL / 4096) return 0;  // (row * 768 floats of the QKV buffer is indexed in 32 bits by the GEMM epilogues)
+  const int R = (int)rows;
+  const int S = cn_score_slabs(R, ctx->cfg.vocab_size, ctx->n_cu, ctx->score_vsplit);
+  return dec_ws(ctx, n_audio, t_audio, caps_per_audio * cap_len, 1, nullptr, true).total + cn_score_part_bytes(R, S);
+}
+
+extern "C" int conette_score(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* caps_in,
+                             const int32_t* targets, int32_t n_audio, int32_t t_audio, int32_t caps_per_audio,
+                             int32_t cap_len, float* tok_lprobs, float* sum_lprobs, int32_t* n_tokens, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if (!ctx || !frame_embs || !frame_lens || !caps_in || !targets || !sum_lprobs || !n_tokens || !workspace || n_audio <= 0 ||
+      t_audio <= 0) {
+    cn_set_error("score: bad argument");
+    return CN_ERR_ARG;
+  }
+  if (cap_len < 1 || cap_len > CN_MAX_PRED || cap_len > ctx->pe_len) {
+    cn_set_error("score: cap_len=%d unsupported (1..%d)", cap_len, CN_MAX_PRED);
+    return CN_ERR_ARG;
+  }
+  if (caps_per_audio < 1) {
+    cn_set_error("score: caps_per_audio=%d < 1", caps_per_audio);
+    return CN_ERR_ARG;
+  }
+  if (ctx->cfg.d_model != 256 || ctx->cfg.nhead != 8) {
+    cn_set_error("score: kernels are specialised for d_model=256, nhead=8");
+    return CN_ERR_ARG;
+  }
+  const size_t need = conette_score_workspace_bytes(ctx, n_audio, t_audio, caps_per_audio, cap_len);
+  if (need == 0) {
+    cn_set_error("score: %d x %d x %d rows in one call are too many (split the call)", n_audio, caps_per_audio, cap_len);
+    return CN_ERR_ARG;
+  }
+  if (workspace_bytes < need) {
+    cn_set_error("score: workspace %zu < %zu", workspace_bytes, need);
+    return CN_ERR_WORKSPACE;
+  }
+  const CnScoreOut out{targets, tok_lprobs, sum_lprobs, n_tokens};
+  CN_BY_PRECISION(ctx, forcing_prefill_impl<OT>(ctx, frame_embs, frame_lens, caps_in, n_audio, t_audio, caps_per_audio, cap_len,
+                                                nullptr, &out, (char*)workspace, (hipStream_t)stream));
 }
 
 extern "C" int conette_greedy(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,

@@ -32,6 +32,7 @@ EXPORTS = (
     "conette_set_option", "conette_profile_enable", "conette_profile_read", "conette_stream_create_masked",
     "conette_stream_destroy", "conette_forcing_workspace_bytes", "conette_forcing",
     "conette_greedy_workspace_bytes", "conette_greedy", "conette_decode_graph_nodes", "conette_encode_nonfinite",
+    "conette_score_workspace_bytes", "conette_score",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -74,6 +75,7 @@ OPT_DECODE_GRAPH = 1
 OPT_DECODE_FUSION = 2
 OPT_ENCODE_RESERVED_CUS = 3
 OPT_FORCING_STEPWISE = 4
+OPT_SCORE_VSPLIT = 5
 MAX_DECODE_GRAPHS = 64   # CONETTE_MAX_DECODE_GRAPHS: decode hipGraphs (= persistent buffer sets) kept per context
 PROF_CLASSES = ("frontend", "stem", "dwconv_ln", "pw1_gemm", "pw2_gemm", "downsample", "heads", "dec_prepare",
                 "dec_gemm", "dec_attn", "dec_misc", "search")
@@ -134,6 +136,11 @@ def load_library() -> C.CDLL:
     lib.conette_forcing.restype = C.c_int
     lib.conette_forcing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_score_workspace_bytes.restype = C.c_size_t
+    lib.conette_score_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_score.restype = C.c_int
+    lib.conette_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.conette_greedy_workspace_bytes.restype = C.c_size_t
     lib.conette_greedy_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.conette_greedy.restype = C.c_int
@@ -570,6 +577,53 @@ class Engine:
                                       wsb.numel(), _stream())
         _check(st, "conette_forcing")
         return out
+
+    def score(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, caps_in: torch.Tensor, targets: torch.Tensor,
+              caps_per_audio: int = 1, want_tokens: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+        """Log-likelihoods of given captions (conette_score, include/conette_hip.h): frame_embs (N, T, 768), caps_in / targets
+        (N * caps_per_audio, cap_len) ids (scoring.split_captions; caption p belongs to clip p // caps_per_audio) ->
+        {"tok_lprobs": (P, cap_len) fp32 or None, "sum_lprobs": (P,) fp32, "n_tokens": (P,) int32}.  No logits are written.
+        ``caps_in`` is held to [0, vocab) before the call (the embedding lookup trusts it; skipped while the stream is being
+        captured, where nothing may be read back).  A call whose workspace would exceed ``score_workspace_bound`` bytes
+        (default scoring.SCORE_WORKSPACE_BOUND, 1 GiB) runs as several calls over clips -- or, when one clip's captions alone
+        exceed it, over slices of its captions -- with equal results."""
+        from . import scoring
+        n, t, _ = frame_embs.shape
+        cpa, cap_len = int(caps_per_audio), int(caps_in.shape[1])
+        if cpa < 1 or caps_in.ndim != 2 or tuple(caps_in.shape) != tuple(targets.shape) or caps_in.shape[0] != n * cpa:
+            raise ValueError(f"score: caps_in {tuple(caps_in.shape)} / targets {tuple(targets.shape)} do not hold "
+                             f"{n} x {cpa} captions of one length")
+        if not torch.cuda.is_current_stream_capturing() and caps_in.numel() > 0:
+            lo, hi = int(caps_in.min()), int(caps_in.max())
+            if lo < 0 or hi >= self.vocab_size:
+                raise ValueError(f"score: caps_in ids must lie in [0, {self.vocab_size}), found [{lo}, {hi}]")
+        fe = frame_embs.to(self.device, torch.float32).contiguous()
+        lens = frame_lens.to(self.device, torch.int32).contiguous()
+        caps = caps_in.to(self.device, torch.int32).contiguous()
+        tgt = targets.to(self.device, torch.int32).contiguous()
+        p = n * cpa
+        tok = torch.empty((p, cap_len), dtype=torch.float32, device=self.device) if want_tokens else None
+        sums = torch.empty((p,), dtype=torch.float32, device=self.device)
+        cnt = torch.empty((p,), dtype=torch.int32, device=self.device)
+        ctx = self._ctx_dec
+        # (0 = more rows than one call takes: never fits)
+        need = lambda nc, mc: int(self.lib.conette_score_workspace_bytes(ctx, nc, t, mc, cap_len)) or (1 << 62)
+        bound = int(getattr(self, "score_workspace_bound", scoring.SCORE_WORKSPACE_BOUND))
+        for i0, nc, j0, mc in scoring.plan_chunks(n, cpa, need, bound):
+            if mc == cpa:     # whole clips: their captions are one contiguous run of rows
+                rows = slice(i0 * cpa, (i0 + nc) * cpa)
+            else:             # a slice of one clip's captions
+                rows = slice(i0 * cpa + j0, i0 * cpa + j0 + mc)
+            wsb = self._workspace("score", need(nc, mc))
+            st = self.lib.conette_score(ctx, _ptr(fe[i0:i0 + nc]), _ptr(lens[i0:i0 + nc]), _ptr(caps[rows]), _ptr(tgt[rows]), nc, t, mc,
+                                        cap_len, _ptr(None if tok is None else tok[rows]), _ptr(sums[rows]), _ptr(cnt[rows]),
+                                        _ptr(wsb), wsb.numel(), _stream())
+            _check(st, "conette_score")
+        return {"tok_lprobs": tok, "sum_lprobs": sums, "n_tokens": cnt}
+
+    def set_score_vsplit(self, slabs: int) -> None:
+        """Vocabulary slabs of conette_score's fused kernel: 0 = chosen from the row count (default), k >= 1 = k (clamped)."""
+        _check(self.lib.conette_set_option(self._ctx_dec, OPT_SCORE_VSPLIT, int(slabs)), "set_option")
 
     def greedy(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, bos_ids: torch.Tensor,
                forbid_mask: Optional[torch.Tensor], min_pred: int, max_pred: int) -> Dict[str, torch.Tensor]:

@@ -369,6 +369,59 @@ class CoNeTTEModel:
         logits = self.engine.forcing(audio, lens, caps_in)  # (B, cap_len, V)
         return logits.permute(0, 2, 1)
 
+    def score_captions(self, x, captions: Tensor, sr=None, x_shapes=None, preprocess: bool = True,
+                       task: Union[str, List[str], None] = None, pairwise: bool = False) -> Dict[str, Tensor]:
+        """How likely given captions are for given clips -- the quantity CoNeTTEPLM.validation_step / test_step report
+        (pl_modules/conette.py:233-336: forcing logits of every reference caption -> CrossEntropyLossMean(ignore_index=pad_id,
+        dim=1), nn/loss/ce_mean.py:30-34), computed without materialising logits (conette_score).
+
+        ``x`` as in ``teacher_forcing``.  ``captions``: integer ids (B, L) or (B, n_caps, L) -- FULL captions: first token,
+        words, <eos>, pad_id; with ``pairwise=True`` (M, L), every caption scored against every clip (n_caps = M: a B x M
+        retrieval matrix; projection and cross-attention keys / values run once per clip).  ``task`` as in ``forward``: a
+        first token equal to <bos> is replaced by the clip's task token; without a task a <bos> raises the reference's error.
+        Returns {"lprobs": (B, n_caps, L - 1) per-token log-probabilities (0 at pads), "sum_lprobs" / "n_tokens": (B, n_caps),
+        "losses": (B, n_caps) the reference's ``losses``, "loss": their mean}.  Precision "certified" scores through its
+        16-bit base context, like ``teacher_forcing``."""
+        from . import scoring
+        captions = torch.as_tensor(captions)
+        if captions.is_floating_point() or captions.ndim not in ((2,) if pairwise else (2, 3)):
+            raise ValueError("captions must be an integer tensor of shape (bsize, caps_size) or (bsize, n_caps, caps_size)"
+                             " -- (n_caps, caps_size) with pairwise=True.")
+        with torch.cuda.device(self.device):
+            if preprocess:
+                batch = self.preprocessor(x, sr, x_shapes)
+                audio, audio_shape = batch["audio"], batch["audio_shape"]
+            elif isinstance(x, dict):
+                audio, audio_shape = x["audio"], x["audio_shape"]
+            else:
+                audio = x
+                audio_shape = x_shapes if x_shapes is not None else torch.as_tensor([list(a.shape) for a in x])
+            if audio.ndim == 4:
+                audio = audio.squeeze(dim=1)
+            bsize = int(audio.shape[0])
+            caps3 = scoring.pairwise_captions(captions, bsize) if pairwise else (captions[:, None] if captions.ndim == 2 else captions)
+            if caps3.shape[0] != bsize:
+                raise ValueError(f"Invalid number of captions {caps3.shape[0]} for {bsize} audio clips.")
+            task_ids = None
+            if task is not None:
+                tasks = [task] * bsize if isinstance(task, str) else list(task)
+                if len(tasks) != bsize:
+                    raise ValueError(f"Invalid number of tasks with input. (found {len(tasks)} tasks but {bsize} elements)")
+                for name in tasks:
+                    if name not in self.config.task_names:
+                        raise ValueError(f"Invalid argument {tasks=}. (task {name} is not in {self.config.task_names})")
+                parts = [name.split("_") for name in tasks]
+                task_ids = self.batch_to_task_token_ids([q[0] for q in parts], ["_".join(q[1:]) if len(q) >= 2 else None for q in parts])
+            caps3 = scoring.replace_bos(caps3.cpu(), self.tokenizer.bos_token_id, task_ids)
+            n_caps, size = int(caps3.shape[1]), int(caps3.shape[2])
+            caps_in, targets = scoring.split_captions(caps3.reshape(bsize * n_caps, size), self.tokenizer.pad_token_id)
+            lens = torch.as_tensor(audio_shape)[:, 1].to(torch.int32)
+            res = self.engine.score(audio, lens, caps_in, targets, caps_per_audio=n_caps)
+            sums, cnt = res["sum_lprobs"].reshape(bsize, n_caps), res["n_tokens"].reshape(bsize, n_caps)
+            losses = scoring.losses_from(sums, cnt)
+            return {"lprobs": res["tok_lprobs"].reshape(bsize, n_caps, size - 1), "sum_lprobs": sums, "n_tokens": cnt,
+                    "losses": losses, "loss": losses.mean()}
+
     def greedy_search(self, x, sr=None, x_shapes=None, preprocess: bool = True, bos_id: Optional[int] = None,
                       min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
                       forbid_rep_mode: Optional[str] = None) -> Tensor:

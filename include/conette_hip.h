@@ -171,6 +171,29 @@ int conette_forcing(conette_ctx* ctx, const float* frame_embs, const int32_t* fr
                     int32_t batch, int32_t t_audio, int32_t cap_len, float* logits, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Scoring of given captions: what CoNeTTEPLM.validation_step / test_step compute from the forcing logits
+ * (pl_modules/conette.py:233-256: decode_audio(..., "forcing") per reference caption, then CrossEntropyLossMean(ignore_index=pad_id,
+ * dim=1), nn/loss/ce_mean.py:30-34) -- the log-probability of every target token, without the logits: the classifier GEMM, the
+ * log-sum-exp over the vocabulary and the gather of the target's logit are one kernel, and no (rows, vocab) array exists
+ * anywhere, the workspace included.  P = n_audio * caps_per_audio captions; caption p belongs to clip p / caps_per_audio, so the
+ * projection and the cross-attention keys / values are computed once per CLIP however many captions are scored against it.
+ *   caps_in    : dev (P, cap_len) int32, conette_forcing's contract (column 0 the task token, right-padded with pad_id, pads
+ *                masked as keys); ids must lie in [0, vocab)
+ *   targets    : dev (P, cap_len) int32, targets[p][t] = the token to be predicted at position t (the reference passes
+ *                captions[:, 1:] for caps_in = captions[:, :-1])
+ *   tok_lprobs : dev (P, cap_len) fp32 or NULL -- log_softmax(logits[p][t])[targets[p][t]]; exactly 0 where the target is pad_id,
+ *                NaN where it lies outside [0, vocab) (the target is compared with column indices, never used as an address)
+ *   sum_lprobs : dev (P) fp32, the sum over the caption's non-pad targets
+ *   n_tokens   : dev (P) int32, their number -- the reference's per-caption loss is -sum_lprobs / n_tokens
+ * cap_len <= 64, caps_per_audio >= 1.  Asynchronous on `stream`, capturable; results are bit-identical from run to run.  Works on
+ * decoder-only contexts.  The workspace size depends on CONETTE_OPT_SCORE_VSPLIT as set when it is asked for. */
+size_t conette_score_workspace_bytes(const conette_ctx* ctx, int32_t n_audio, int32_t t_audio, int32_t caps_per_audio,
+                                     int32_t cap_len);
+int conette_score(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* caps_in,
+                  const int32_t* targets, int32_t n_audio, int32_t t_audio, int32_t caps_per_audio, int32_t cap_len,
+                  float* tok_lprobs, float* sum_lprobs, int32_t* n_tokens, void* workspace, size_t workspace_bytes,
+                  void* stream);
+
 /* greedy_search (nn/decoding/greedy.py:17-131; BaselinePLM's decoder, not reachable from
  * CoNeTTEPLM): the arg-max chain with the full masked logits of every step as output.
  *   logits : dev (B, max_pred, vocab) fp32 -- per step the logits of every unfinished clip with the EOS floor
@@ -206,6 +229,9 @@ int conette_stream_destroy(void* stream);
                                             not queued behind them (0 .. n_cu / 2) */
 #define CONETTE_OPT_FORCING_STEPWISE 4 /* default 0: conette_forcing is one causal pass over all caption positions
                                          (forcing.py:12-71); 1: the KV-cached step kernels fed with the caption */
+#define CONETTE_OPT_SCORE_VSPLIT 5 /* default 0: conette_score picks the number of vocabulary slabs its fused kernel's grid is
+                                     split into from the row count and the compute units (1 at large row counts); k >= 1:
+                                     k slabs, clamped to the number of 128-column tiles of the vocabulary (tests, measurements) */
 int conette_set_option(conette_ctx* ctx, int32_t option, int32_t value);
 
 /* Kernel / copy nodes of the decode hipGraph that conette_decode launched (or captured) most recently on this context
