@@ -30,8 +30,6 @@ if os.environ.get("CN_DB_WIDE_ROWS_SP"):   # A/B build: the same for the exact p
     FLAGS.append("-DDB_WIDE_ROWS_SP=" + os.environ["CN_DB_WIDE_ROWS_SP"])
 if os.environ.get("CN_DB_WIDE_R"):      # A/B build: rows from which a search counts as wide (dec_block.h: 512)
     FLAGS.append("-DDB_WIDE_R=" + os.environ["CN_DB_WIDE_R"])
-if os.environ.get("CN_DB_XCDS"):   # A/B build: XCDs whose workgroups work in the decoder block kernel (dec_block.h: 8 = all)
-    FLAGS.append("-DDB_XCDS=" + os.environ["CN_DB_XCDS"])
 for _k in ("CN_DW96_S", "CN_DW96_TH", "CN_DW192_S", "CN_DW192_TH"):   # A/B builds: tile of the depthwise kernel of stages 0 / 1 (encoder.hip)
     if os.environ.get(_k):
         FLAGS.append(f"-D{_k}=" + os.environ[_k])

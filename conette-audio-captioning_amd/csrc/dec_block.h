@@ -55,9 +55,6 @@
 #ifndef DB_WIDE_R
 #define DB_WIDE_R 512
 #endif
-#ifndef DB_XCDS
-#define DB_XCDS 8   // XCDs whose workgroups work in the block kernel (8 = all: the product)
-#endif
 #ifndef DB_ROWS_SP
 #define DB_ROWS_SP 4  // exact precision: the same (eight rows = two per row wave halve the weight re-streaming: solo search 5.3 -> 6.6 ms, mixed16 beside an encoder +0.3 %; profiles/r04_notes.md)
 #endif
@@ -350,15 +347,7 @@ __global__ __launch_bounds__((DbL<HT, NR>::THREADS), 1) void cn_dec_block_kernel
   float* sP = (float*)(smem + DbL<HT, NR>::OFF_P);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // DB_XCDS < 8 (A/B build knob): only the workgroups dealt to the first DB_XCDS XCDs work (the grid is 8 / DB_XCDS times
-  // larger, the others return at once), so that fewer L2s pull the layer's 768 KB weight stream
-  int bx = blockIdx.x;
-  if (DB_XCDS < 8) {
-    if ((bx & 7) >= DB_XCDS) return;
-    bx = (bx >> 3) * DB_XCDS + (bx & 7);
-    if (bx * NR >= R) return;
-  }
-  const int r0 = bx * NR;
+  const int r0 = blockIdx.x * NR;
 
   if (wave < 4) {
     // ======================= GEMM waves ========================================================

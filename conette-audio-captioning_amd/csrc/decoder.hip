@@ -866,53 +866,173 @@ extern "C" size_t conette_decode_workspace_bytes(const conette_ctx* ctx, int32_t
   return dec_ws(ctx, batch, t_audio, beam, max_pred, nullptr).total;
 }
 
+// Arguments of the step path (decode_impl): conette_decode, conette_forcing (stepwise) and conette_greedy fill them by name.
+// Zeroed with memset, the record is also the key of conette_decode's graph cache, compared bytewise: the buffers and the shape
+// identify a captured launch sequence.  The stream is no part of it, and the three pointers at the end are null on that path.
+struct DecArgs {
+  const float* frame_embs;
+  const int32_t* frame_lens;
+  const int32_t* bos_ids;
+  const uint8_t* forbid;  // may be null
+  int32_t* best_preds;
+  float* best_lprobs;
+  int32_t* mult_preds;
+  float* mult_lprobs;
+  int32_t* out_sizes;
+  float* step0_logits;  // these four outputs are optional (null: not wanted)
+  int32_t* trace_sel;
+  float* trace_val;
+  float* margins;
+  char* ws;
+  int B, Ta, beam, min_pred, maxp;
+  const int32_t* force_caps;  // teacher forcing: beam == 1, maxp == caption length, no search
+  float* force_logits;
+  float* greedy_logits;  // conette_greedy: the masked logits of every step
+  bool operator==(const DecArgs& o) const { return memcmp(this, &o, sizeof(DecArgs)) == 0; }
+};
+
+// ---- once per batch: projection (conette.py:457) and cross K/V of every layer ---------------
 template <typename T>
-static int decode_impl(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
-                       const uint8_t* forbid, int B, int Ta, int beam, int min_pred, int maxp, int32_t* best_preds,
-                       float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
-                       float* step0_logits, int32_t* trace_sel, float* trace_val, char* wsp, hipStream_t s,
-                       const int32_t* force_caps = nullptr, float* force_logits = nullptr,
-                       float* greedy_logits = nullptr, float* margins = nullptr) {
-  const conette_config& cfg = ctx->cfg;
-  const int d = cfg.d_model, NL = cfg.n_layers, R = B * beam, V = cfg.vocab_size, dff = cfg.d_ff;
-  DecWs w = dec_ws(ctx, B, Ta, beam, maxp, wsp);
-  const bool forcing = force_caps != nullptr;  // beam == 1, maxp == caption length, no search
-  const unsigned long long* kvalid = forcing ? w.kvalid : nullptr;
+static int dec_prepare(conette_ctx* ctx, const float* frame_embs, int B, int Ta, const DecWs& w, hipStream_t s) {
+  CnProfScope ps(ctx, CONETTE_PROF_DEC_PREPARE, s);
+  const int d = ctx->cfg.d_model, kv_ld = ctx->cfg.n_layers * 2 * d;
   T* fe_t = (T*)w.fe_t;
   T* mem = (T*)w.mem;
-  T* kvc = (T*)w.kvc;
+  const size_t n = (size_t)B * Ta * CN_FEAT;
+  hipLaunchKernelGGL((cn_cvt_kernel<T>), dim3((unsigned)((n + 1023) / 1024 < 4096 ? (n + 1023) / 1024 : 4096)), dim3(256), 0, s,
+                     frame_embs, fe_t, n);
+  CN_LAUNCH_CHECK();
+  EpiBiasAct<T, ACT_RELU> ep{ctx->proj_b, mem, d, ACT_RELU};
+  CN_TRY(cn_mm(fe_t, CN_FEAT, (const T*)ctx->proj_w, CN_FEAT, B * Ta, d, CN_FEAT, ep, s));
+  EpiBiasAct<T, ACT_NONE> ekv{ctx->kv_b, (T*)w.kvc, kv_ld, ACT_NONE};
+  CN_TRY(cn_mm(mem, d, (const T*)ctx->kv_w, d, B * Ta, kv_ld, d, ekv, s));
+  return CN_OK;
+}
+
+// ---- decoder layer l, one launch per sub-layer, on the R rows of w.x / w.xt ------------------------------------------------
+// QKV GEMM, self-attention, out-proj + residual, LN1, cross-Q GEMM, cross-attention, out-proj + residual, LN2, FFN1, FFN2, LN3.
+// The step path without the block kernel and the one-pass teacher forcing both run it; what they differ in:
+//   self_attn(l)   launches the layer's self-attention from w.qkv into w.attn_t: the KV-cached step kernel, or the causal one
+//   rows_per_clip  consecutive rows that attend to one clip's audio memory (the "beam" of the cross-attention kernel)
+//   ffn2_split     FFN2 as split-K slabs summed by LN3 (16-bit and exact operands only: fp32 has no such GEMM) instead of one
+//                  GEMM with bias + residual in its epilogue.  The two sum in different orders, so a caller never changes its choice.
+template <typename T, typename SelfAttn>
+static int dec_sublayer_layer(conette_ctx* ctx, const DecWs& w, int l, const int32_t* frame_lens, int R, int Ta, int rows_per_clip,
+                              bool ffn2_split, SelfAttn self_attn, hipStream_t s) {
+  const CnLayerW& lw = ctx->layers[l];
+  const int d = ctx->cfg.d_model, dff = ctx->cfg.d_ff, kv_ld = ctx->cfg.n_layers * 2 * d;
+  const float scale = 1.0f / sqrtf((float)(d / ctx->cfg.nhead));
+  const int rblocks = cn_cdiv(R, 4);
   T* xt = (T*)w.xt;
   T* attn_t = (T*)w.attn_t;
+  T* ffh = (T*)w.ffh;
+  auto ln_tmp = [&](const float* g, const float* b) -> int {  // LayerNorm of w.tmp, a GEMM output that holds bias + residual already
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
+    hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.tmp, 1, (size_t)0, (const float*)nullptr,
+                       (const float*)nullptr, g, b, R, w.x, xt);
+    CN_LAUNCH_CHECK();
+    return CN_OK;
+  };
+  {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+    EpiBiasAct<float, ACT_NONE> eq{lw.sa_in_b, w.qkv, 3 * d, ACT_NONE};
+    CN_TRY(cn_mm(xt, d, (const T*)lw.sa_in_w, d, R, 3 * d, d, eq, s));
+  }
+  {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
+    self_attn(l);
+    CN_LAUNCH_CHECK();
+  }
+  {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+    EpiResid eo{lw.sa_out_b, nullptr, w.x, w.tmp, d};
+    CN_TRY(cn_mm(attn_t, d, (const T*)lw.sa_out_w, d, R, d, d, eo, s));
+  }
+  CN_TRY(ln_tmp(lw.n1w, lw.n1b));
+  {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+    EpiBiasAct<float, ACT_NONE> ecq{lw.ca_q_b, w.q, d, ACT_NONE};
+    CN_TRY(cn_mm(xt, d, (const T*)lw.ca_q_w, d, R, d, d, ecq, s));
+  }
+  {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
+    hipLaunchKernelGGL((cn_cross_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, (T*)w.kvc, kv_ld, l * 2 * d, frame_lens, R,
+                       rows_per_clip, Ta, scale, attn_t);
+    CN_LAUNCH_CHECK();
+  }
+  {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+    EpiResid eco{lw.ca_out_b, nullptr, w.x, w.tmp, d};
+    CN_TRY(cn_mm(attn_t, d, (const T*)lw.ca_out_w, d, R, d, d, eco, s));
+  }
+  CN_TRY(ln_tmp(lw.n2w, lw.n2b));
+  {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+    EpiBiasAct<T, CnGeluAct<T>::value> e1{lw.ff1_b, ffh, dff, CnGeluAct<T>::value};
+    CN_TRY(cn_mm(xt, d, (const T*)lw.ff1_w, d, R, dff, d, e1, s));
+  }
+  int nslab = 0;  // slabs FFN2 wrote for LN3 to sum; 0: FFN2 finished its sum in w.tmp
+  if (ffn2_split) {
+    CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+    EpiSlab e2{w.slabs, d, (size_t)R * d};
+    if constexpr (CnIsH16<T>::value) {
+      // K = d_ff is long and M = R is small: split K over blockIdx.y into partial slabs, summed
+      // (fixed order, with bias + residual) by the LayerNorm kernel that follows
+      const int splits = (dff % (FF2_SPLITS * 64) == 0) ? FF2_SPLITS : 1;
+      CN_TRY(cn_gemm2(ffh, dff, (const T*)lw.ff2_w, dff, R, d, dff, e2, s, splits));
+      nslab = splits;
+    } else if constexpr (std::is_same<T, sp16_t>::value) {
+      // exact precision: the same split-K as bf16 (M = R rows, K = d_ff: 12 blocks looping over 64 k-tiles took 30 us,
+      // a quarter of the whole decode) -- partial slabs, summed in a fixed order with bias + residual by the LayerNorm
+      const int splits = (dff % (FF2_SPLITS * 32) == 0) ? FF2_SPLITS : 1;
+      CN_TRY(cn_gemm2_sp((const sp16_t*)ffh, dff, (const sp16_t*)lw.ff2_w, dff, R, d, dff, e2, s, splits));
+      nslab = splits;
+    }
+  }
+  if (nslab == 0) {
+    {
+      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+      EpiResid e2{lw.ff2_b, nullptr, w.x, w.tmp, d};
+      CN_TRY(cn_mm(ffh, dff, (const T*)lw.ff2_w, dff, R, d, dff, e2, s));
+    }
+    return ln_tmp(lw.n3w, lw.n3b);
+  }
+  CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
+  hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.slabs, nslab, (size_t)R * d, lw.ff2_b, w.x, lw.n3w,
+                     lw.n3b, R, w.x, xt);
+  CN_LAUNCH_CHECK();
+  return CN_OK;
+}
+
+template <typename T>
+static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
+  const conette_config& cfg = ctx->cfg;
+  const int B = a.B, Ta = a.Ta, beam = a.beam, min_pred = a.min_pred, maxp = a.maxp;
+  const int d = cfg.d_model, NL = cfg.n_layers, R = B * beam, V = cfg.vocab_size, dff = cfg.d_ff;
+  DecWs w = dec_ws(ctx, B, Ta, beam, maxp, a.ws);
+  const bool forcing = a.force_caps != nullptr;
+  const unsigned long long* kvalid = forcing ? w.kvalid : nullptr;
+  T* kvc = (T*)w.kvc;
+  T* xt = (T*)w.xt;
   T* ffh = (T*)w.ffh;
   const int kv_ld = NL * 2 * d;
   const float scale = 1.0f / sqrtf((float)(d / cfg.nhead));
   const int rblocks = cn_cdiv(R, 4);
 
-  // ---- once per batch: projection (conette.py:457) and cross K/V of every layer ---------------
-  {
-    CnProfScope ps(ctx, CONETTE_PROF_DEC_PREPARE, s);
-    const size_t n = (size_t)B * Ta * CN_FEAT;
-    hipLaunchKernelGGL((cn_cvt_kernel<T>), dim3((unsigned)((n + 1023) / 1024 < 4096 ? (n + 1023) / 1024 : 4096)), dim3(256), 0, s,
-                       frame_embs, fe_t, n);
-    CN_LAUNCH_CHECK();
-    EpiBiasAct<T, ACT_RELU> ep{ctx->proj_b, mem, d, ACT_RELU};
-    CN_TRY(cn_mm(fe_t, CN_FEAT, (const T*)ctx->proj_w, CN_FEAT, B * Ta, d, CN_FEAT, ep, s));
-    EpiBiasAct<T, ACT_NONE> ekv{ctx->kv_b, kvc, kv_ld, ACT_NONE};
-    CN_TRY(cn_mm(mem, d, (const T*)ctx->kv_w, d, B * Ta, kv_ld, d, ekv, s));
-  }
-  hipLaunchKernelGGL(cn_init_state_kernel, dim3(64), dim3(256), 0, s, B, beam, maxp, bos_ids, w.n_active, w.slot,
-                     w.sum_lp, w.prefix, w.anc, w.cur_tok, mult_preds, mult_lprobs, w.out_len, out_sizes, cfg.pad_id,
-                     trace_sel, trace_val, w.live, margins);
+  CN_TRY(dec_prepare<T>(ctx, a.frame_embs, B, Ta, w, s));
+  hipLaunchKernelGGL(cn_init_state_kernel, dim3(64), dim3(256), 0, s, B, beam, maxp, a.bos_ids, w.n_active, w.slot,
+                     w.sum_lp, w.prefix, w.anc, w.cur_tok, a.mult_preds, a.mult_lprobs, w.out_len, a.out_sizes, cfg.pad_id,
+                     a.trace_sel, a.trace_val, w.live, a.margins);
   CN_LAUNCH_CHECK();
   if (forcing) {
-    hipLaunchKernelGGL(cn_force_init_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, force_caps, B, maxp, cfg.pad_id,
+    hipLaunchKernelGGL(cn_force_init_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, a.force_caps, B, maxp, cfg.pad_id,
                        w.kvalid, w.anc);
     CN_LAUNCH_CHECK();
   }
 
   for (int step = 0; step < maxp; ++step) {
     if (forcing) {
-      hipLaunchKernelGGL(cn_force_tok_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, force_caps, B, maxp, step, w.cur_tok);
+      hipLaunchKernelGGL(cn_force_tok_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, a.force_caps, B, maxp, step, w.cur_tok);
       CN_LAUNCH_CHECK();
     }
     // fused path (dec_block.h + dec_ffn.h): 16-bit operands, and since round 4 the exact precision (hi / lo passes of the same
@@ -969,9 +1089,9 @@ static int decode_impl(conette_ctx* ctx, const float* frame_embs, const int32_t*
           auto launch_block = [&](auto nr_tag) -> int {
             constexpr int NR = decltype(nr_tag)::value;
             CN_TRY((cn_dec_block_setup<T, NR>()));
-            hipLaunchKernelGGL((cn_dec_block_kernel<T, NR>), dim3(DB_XCDS < 8 ? 8 * cn_cdiv(cn_cdiv(R, NR), DB_XCDS) : cn_cdiv(R, NR)), dim3((DbL<T, NR>::THREADS)), (DbL<T, NR>::BYTES), s, pro, wt, kc, vc,
-                               w.anc, step, R, beam, maxp, (const T*)kvc, kv_ld, l * 2 * d, frame_lens, Ta, w.x, xt,
-                               scale, kvalid, db_debug, gate);
+            hipLaunchKernelGGL((cn_dec_block_kernel<T, NR>), dim3(cn_cdiv(R, NR)), dim3((DbL<T, NR>::THREADS)), (DbL<T, NR>::BYTES), s,
+                               pro, wt, kc, vc, w.anc, step, R, beam, maxp, (const T*)kvc, kv_ld, l * 2 * d, a.frame_lens, Ta, w.x,
+                               xt, scale, kvalid, db_debug, gate);
             CN_LAUNCH_CHECK();
             return CN_OK;
           };
@@ -1012,122 +1132,38 @@ static int decode_impl(conette_ctx* ctx, const float* frame_embs, const int32_t*
       }
     }
     if (!fused_done) {
-      for (int l = 0; l < NL; ++l) {
-        const CnLayerW& lw = ctx->layers[l];
+      auto self_attn = [&](int l) {
         T* kc = (T*)w.kc + (size_t)l * maxp * R * d;
         T* vc = (T*)w.vc + (size_t)l * maxp * R * d;
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-          EpiBiasAct<float, ACT_NONE> eq{lw.sa_in_b, w.qkv, 3 * d, ACT_NONE};
-          CN_TRY(cn_mm(xt, d, (const T*)lw.sa_in_w, d, R, 3 * d, d, eq, s));
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
-          hipLaunchKernelGGL((cn_self_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.qkv, kc, vc, w.anc, step, R,
-                             beam, maxp, scale, attn_t, kvalid);
-          CN_LAUNCH_CHECK();
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-          EpiResid eo{lw.sa_out_b, nullptr, w.x, w.tmp, d};
-          CN_TRY(cn_mm(attn_t, d, (const T*)lw.sa_out_w, d, R, d, d, eo, s));
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
-          hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.tmp, 1, (size_t)0, (const float*)nullptr,
-                             (const float*)nullptr, lw.n1w, lw.n1b, R, w.x, xt);
-          CN_LAUNCH_CHECK();
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-          EpiBiasAct<float, ACT_NONE> ecq{lw.ca_q_b, w.q, d, ACT_NONE};
-          CN_TRY(cn_mm(xt, d, (const T*)lw.ca_q_w, d, R, d, d, ecq, s));
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
-          hipLaunchKernelGGL((cn_cross_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, kvc, kv_ld, l * 2 * d,
-                             frame_lens, R, beam, Ta, scale, attn_t);
-          CN_LAUNCH_CHECK();
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-          EpiResid eco{lw.ca_out_b, nullptr, w.x, w.tmp, d};
-          CN_TRY(cn_mm(attn_t, d, (const T*)lw.ca_out_w, d, R, d, d, eco, s));
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
-          hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.tmp, 1, (size_t)0, (const float*)nullptr,
-                             (const float*)nullptr, lw.n2w, lw.n2b, R, w.x, xt);
-          CN_LAUNCH_CHECK();
-        }
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-          EpiBiasAct<T, CnGeluAct<T>::value> e1{lw.ff1_b, ffh, dff, CnGeluAct<T>::value};
-          CN_TRY(cn_mm(xt, d, (const T*)lw.ff1_w, d, R, dff, d, e1, s));
-        }
-        if constexpr (CnIsH16<T>::value) {
-          // K = d_ff is long and M = R is small: split K over blockIdx.y into partial slabs, summed
-          // (fixed order, with bias + residual) by the LayerNorm kernel that follows
-          const int splits = (dff % (FF2_SPLITS * 64) == 0) ? FF2_SPLITS : 1;
-          {
-            CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-            EpiSlab e2{w.slabs, d, (size_t)R * d};
-            CN_TRY(cn_gemm2(ffh, dff, (const T*)lw.ff2_w, dff, R, d, dff, e2, s, splits));
-          }
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
-          hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.slabs, splits, (size_t)R * d,
-                             lw.ff2_b, w.x, lw.n3w, lw.n3b, R, w.x, xt);
-          CN_LAUNCH_CHECK();
-        } else if constexpr (std::is_same<T, sp16_t>::value) {
-          // exact precision: the same split-K as bf16 (M = R rows, K = d_ff: 12 blocks looping over 64 k-tiles took 30 us,
-          // a quarter of the whole decode) -- partial slabs, summed in a fixed order with bias + residual by the LayerNorm
-          const int splits = (dff % (FF2_SPLITS * 32) == 0) ? FF2_SPLITS : 1;
-          {
-            CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-            EpiSlab e2{w.slabs, d, (size_t)R * d};
-            CN_TRY(cn_gemm2_sp((const sp16_t*)ffh, dff, (const sp16_t*)lw.ff2_w, dff, R, d, dff, e2, s, splits));
-          }
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
-          hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.slabs, splits, (size_t)R * d,
-                             lw.ff2_b, w.x, lw.n3w, lw.n3b, R, w.x, xt);
-          CN_LAUNCH_CHECK();
-        } else {
-          {
-            CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-            EpiResid e2{lw.ff2_b, nullptr, w.x, w.tmp, d};
-            CN_TRY(cn_mm(ffh, dff, (const T*)lw.ff2_w, dff, R, d, dff, e2, s));
-          }
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
-          hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.tmp, 1, (size_t)0,
-                             (const float*)nullptr, (const float*)nullptr, lw.n3w, lw.n3b, R, w.x, xt);
-          CN_LAUNCH_CHECK();
-        }
-      }
+        hipLaunchKernelGGL((cn_self_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.qkv, kc, vc, w.anc, step, R, beam, maxp,
+                           scale, (T*)w.attn_t, kvalid);
+      };
+      for (int l = 0; l < NL; ++l) CN_TRY((dec_sublayer_layer<T>(ctx, w, l, a.frame_lens, R, Ta, beam, kBlockT, self_attn, s)));
       {
         CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
         EpiBiasAct<float, ACT_NONE> ec{ctx->cls_b, w.logits, w.ldv, ACT_NONE};
         CN_TRY(cn_mm(xt, d, (const T*)ctx->cls_w, d, R, V, d, ec, s));
       }
     }
-    if (step == 0 && step0_logits)
-      CN_HIP(hipMemcpyAsync(step0_logits, w.logits, (size_t)R * w.ldv * 4, hipMemcpyDeviceToDevice, s));
+    if (step == 0 && a.step0_logits)
+      CN_HIP(hipMemcpyAsync(a.step0_logits, w.logits, (size_t)R * w.ldv * 4, hipMemcpyDeviceToDevice, s));
     if (forcing) {
       hipLaunchKernelGGL(cn_force_store_kernel, dim3(cn_cdiv(V, 1024), R), dim3(256), 0, s, w.logits, w.ldv, V, maxp, step,
-                         force_logits);
+                         a.force_logits);
       CN_LAUNCH_CHECK();
       continue;
     }
-    if (greedy_logits) {  // beam == 1: rows == clips; before the search step updates prefix / n_active
+    if (a.greedy_logits) {  // beam == 1: rows == clips; before the search step updates prefix / n_active
       hipLaunchKernelGGL(cn_greedy_logits_kernel, dim3(cn_cdiv(V, 1024), B), dim3(256), 0, s, w.logits, w.ldv, V, maxp, step,
-                         min_pred, cfg.eos_id, cfg.pad_id, forbid, w.n_active, w.prefix, greedy_logits);
+                         min_pred, cfg.eos_id, cfg.pad_id, a.forbid, w.n_active, w.prefix, a.greedy_logits);
       CN_LAUNCH_CHECK();
     }
     CnProfScope ps_search(ctx, CONETTE_PROF_SEARCH, s);
     if (V <= S3_T * S3_VPT && beam <= 8) {  // register-resident step (one block of 1024 threads per clip)
 #define S3_LAUNCH(NR_, VPT_)                                                                                          \
   hipLaunchKernelGGL((cn_search_step3_kernel<NR_, VPT_>), dim3(B), dim3(S3_T), 0, s, w.logits, w.ldv, V, beam, maxp,  \
-                     step, min_pred, cfg.eos_id, forbid, w.n_active, w.slot, w.sum_lp, w.prefix, w.anc, w.cur_tok,    \
-                     mult_preds, mult_lprobs, w.out_len, trace_sel, trace_val, db_debug, w.live, margins)
+                     step, min_pred, cfg.eos_id, a.forbid, w.n_active, w.slot, w.sum_lp, w.prefix, w.anc, w.cur_tok,    \
+                     a.mult_preds, a.mult_lprobs, w.out_len, a.trace_sel, a.trace_val, db_debug, w.live, a.margins)
       const int vpt = cn_cdiv(V, S3_T);
       if (beam <= 4) {
         if (vpt <= 2) S3_LAUNCH(4, 2);
@@ -1141,28 +1177,23 @@ static int decode_impl(conette_ctx* ctx, const float* frame_embs, const int32_t*
 #undef S3_LAUNCH
     } else {  // vocabularies beyond 8192 entries, beams beyond 8: the generic step (masking in place, top-k over global memory)
       hipLaunchKernelGGL(cn_search_step_kernel, dim3(B), dim3(256), 0, s, w.logits, w.ldv, V, beam, maxp, step,
-                         min_pred, cfg.eos_id, forbid, w.n_active, w.slot, w.sum_lp, w.prefix, w.anc, w.cur_tok,
-                         mult_preds, mult_lprobs, w.out_len, trace_sel, trace_val, w.live, margins);
+                         min_pred, cfg.eos_id, a.forbid, w.n_active, w.slot, w.sum_lp, w.prefix, w.anc, w.cur_tok,
+                         a.mult_preds, a.mult_lprobs, w.out_len, a.trace_sel, a.trace_val, w.live, a.margins);
     }
     CN_LAUNCH_CHECK();
   }
   if (forcing) return CN_OK;
-  hipLaunchKernelGGL(cn_finalize_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, B, beam, maxp, cfg.eos_id, mult_preds,
-                     mult_lprobs, w.out_len, best_preds, best_lprobs, w.eos_idx, out_sizes, margins);
+  hipLaunchKernelGGL(cn_finalize_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, B, beam, maxp, cfg.eos_id, a.mult_preds,
+                     a.mult_lprobs, w.out_len, a.best_preds, a.best_lprobs, w.eos_idx, a.out_sizes, a.margins);
   CN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cn_finalize2_kernel, dim3(1), dim3(256), 0, s, B, w.eos_idx, out_sizes);
+  hipLaunchKernelGGL(cn_finalize2_kernel, dim3(1), dim3(256), 0, s, B, w.eos_idx, a.out_sizes);
   CN_LAUNCH_CHECK();
   return CN_OK;
 }
 
 // ---- hipGraph replay of the (static) decode launch sequence ---------------------------------------
-struct DecKey {
-  const void *fe, *lens, *bos, *forbid, *bp, *bl, *mp, *ml, *sz, *s0, *ts, *tv, *mg, *ws;
-  int B, Ta, beam, min_pred, maxp;
-  bool operator==(const DecKey& o) const { return memcmp(this, &o, sizeof(DecKey)) == 0; }
-};
 struct DecGraph {
-  DecKey key;
+  DecArgs key;
   hipGraphExec_t exec;
   hipGraph_t graph;
   hipEvent_t last;  // recorded behind every launch of `exec`: what an eviction waits for (never the whole device)
@@ -1256,53 +1287,39 @@ extern "C" int conette_set_option(conette_ctx* ctx, int32_t option, int32_t valu
   return CN_ERR_ARG;
 }
 
-extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens,
-                              const int32_t* bos_ids, const uint8_t* forbid_mask, int32_t batch, int32_t t_audio,
-                              int32_t beam, int32_t min_pred, int32_t max_pred, int32_t* best_preds,
-                              float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
-                              float* step0_logits, int32_t* trace_sel, float* trace_val, float* margins,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-  if (!ctx || !frame_embs || !frame_lens || !bos_ids || !best_preds || !best_lprobs || !mult_preds || !mult_lprobs ||
-      !out_sizes || !workspace || batch <= 0 || t_audio <= 0) {
-    cn_set_error("decode: bad argument");
-    return CN_ERR_ARG;
-  }
-  if (beam < 1 || beam > CN_MAX_BEAM || max_pred < 1 || max_pred > CN_MAX_PRED || min_pred < 0) {
-    cn_set_error("decode: beam=%d (1..%d) max_pred=%d (1..%d) min_pred=%d unsupported", beam, CN_MAX_BEAM, max_pred,
-                 CN_MAX_PRED, min_pred);
+// The shared refusals of the decoder entry points, `who` being the prefix of their messages.  dec_check_model: the length (caption
+// length or max_pred, with the entry point's own message: `len_fmt` and its arguments) and the architecture the kernels are
+// specialised for; dec_check_workspace: the workspace.  conette_score has a check of its own between the two.
+template <typename... A>
+static int dec_check_model(const conette_ctx* ctx, const char* who, int len, int min_pred, const char* len_fmt, A... len_args) {
+  if (len < 1 || len > CN_MAX_PRED || len > ctx->pe_len || min_pred < 0) {
+    cn_set_error(len_fmt, len_args...);
     return CN_ERR_ARG;
   }
   if (ctx->cfg.d_model != 256 || ctx->cfg.nhead != 8) {
-    cn_set_error("decode: kernels are specialised for d_model=256, nhead=8");
+    cn_set_error("%s: kernels are specialised for d_model=256, nhead=8", who);
     return CN_ERR_ARG;
   }
-  if (max_pred > ctx->pe_len) {
-    cn_set_error("decode: max_pred exceeds positional table");
-    return CN_ERR_ARG;
-  }
-  const size_t need = conette_decode_workspace_bytes(ctx, batch, t_audio, beam, max_pred);
+  return CN_OK;
+}
+static int dec_check_workspace(const char* who, size_t workspace_bytes, size_t need) {
   if (workspace_bytes < need) {
-    cn_set_error("decode: workspace %zu < %zu", workspace_bytes, need);
+    cn_set_error("%s: workspace %zu < %zu", who, workspace_bytes, need);
     return CN_ERR_WORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  auto run = [&]() -> int {
-    CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, frame_embs, frame_lens, bos_ids, forbid_mask, batch, t_audio, beam, min_pred,
-                                 max_pred, best_preds, best_lprobs, mult_preds, mult_lprobs, out_sizes, step0_logits,
-                                 trace_sel, trace_val, (char*)workspace, s, nullptr, nullptr, nullptr, margins));
-  };
+  return CN_OK;
+}
+
+// `run` (the launch sequence of the decode that `key` identifies) through the context's graph cache: eagerly at the first sighting
+// of a key, captured at the second, replayed from then on.
+template <typename Run>
+static int dec_graph_run(conette_ctx* ctx, const DecArgs& key, hipStream_t s, Run run) {
   DecGraphCache* cache = graph_cache(ctx, true);
   const uint32_t dec_classes = (1u << CONETTE_PROF_DEC_PREPARE) | (1u << CONETTE_PROF_DEC_GEMM) |
                                (1u << CONETTE_PROF_DEC_ATTN) | (1u << CONETTE_PROF_DEC_MISC) |
                                (1u << CONETTE_PROF_SEARCH);
   if (!cache || (ctx->prof_mask & dec_classes) != 0) return run();
 
-  DecKey key;
-  memset(&key, 0, sizeof(key));
-  key.fe = frame_embs, key.lens = frame_lens, key.bos = bos_ids, key.forbid = forbid_mask, key.bp = best_preds;
-  key.bl = best_lprobs, key.mp = mult_preds, key.ml = mult_lprobs, key.sz = out_sizes, key.s0 = step0_logits;
-  key.ts = trace_sel, key.tv = trace_val, key.mg = margins, key.ws = workspace;
-  key.B = batch, key.Ta = t_audio, key.beam = beam, key.min_pred = min_pred, key.maxp = max_pred;
   auto find = [&]() -> DecGraph* {  // (under the lock) least recently used first: a hit moves to the back
     for (int i = 0; i < cache->n; ++i)
       if (cache->g[i].key == key) {
@@ -1344,7 +1361,7 @@ extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const i
       }
       DecGraph* fresh = &cache->g[cache->n++];
       memset(fresh, 0, sizeof(*fresh));
-      fresh->key = key;
+      memcpy(&fresh->key, &key, sizeof(key));  // (every byte: the keys are compared bytewise)
       fresh->seen = 1;
     }
   }
@@ -1352,40 +1369,24 @@ extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const i
   if (todo == EAGER) return run();
 
   // capture, instantiate, launch -- outside the lock; the entry is found again by its key when the graph exists
-  auto give_up = [&]() -> int {   // capture is not available here: every later call runs eagerly
-    std::lock_guard<std::mutex> lock(cache->mu);
-    cache->enabled = 0;
-    return CN_OK;
-  };
-  hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
-  if (ce != hipSuccess) {
-    (void)hipGetLastError();
-    give_up();
-    return run();
-  }
-  const int rc = run();
   hipGraph_t graph = nullptr;
-  ce = hipStreamEndCapture(s, &graph);
-  if (rc != CN_OK || ce != hipSuccess || graph == nullptr) {
-    (void)hipGetLastError();
-    if (graph) (void)hipGraphDestroy(graph);
-    give_up();
-    return run();
-  }
   hipGraphExec_t exec = nullptr;
-  ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  if (ce != hipSuccess || exec == nullptr) {
-    (void)hipGetLastError();
-    (void)hipGraphDestroy(graph);
-    give_up();
-    return run();
-  }
   hipEvent_t last = nullptr;
-  if (hipEventCreateWithFlags(&last, hipEventDisableTiming) != hipSuccess) {
+  auto capture = [&]() -> bool {
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) return false;
+    const int rc = run();
+    if (hipStreamEndCapture(s, &graph) != hipSuccess || rc != CN_OK || graph == nullptr) return false;
+    if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess || exec == nullptr) return false;
+    return hipEventCreateWithFlags(&last, hipEventDisableTiming) == hipSuccess;
+  };
+  if (!capture()) {  // capture is not available here: every later call runs eagerly, and so does this one
     (void)hipGetLastError();
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-    give_up();
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    {
+      std::lock_guard<std::mutex> lock(cache->mu);
+      cache->enabled = 0;
+    }
     return run();
   }
   size_t n_nodes = 0;
@@ -1409,6 +1410,35 @@ extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const i
   tmp.exec = exec, tmp.graph = graph, tmp.last = last;
   dec_graph_release(tmp);
   return CN_OK;
+}
+
+extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens,
+                              const int32_t* bos_ids, const uint8_t* forbid_mask, int32_t batch, int32_t t_audio,
+                              int32_t beam, int32_t min_pred, int32_t max_pred, int32_t* best_preds,
+                              float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
+                              float* step0_logits, int32_t* trace_sel, float* trace_val, float* margins,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ctx || !frame_embs || !frame_lens || !bos_ids || !best_preds || !best_lprobs || !mult_preds || !mult_lprobs ||
+      !out_sizes || !workspace || batch <= 0 || t_audio <= 0) {
+    cn_set_error("decode: bad argument");
+    return CN_ERR_ARG;
+  }
+  if (beam < 1 || beam > CN_MAX_BEAM || max_pred < 1 || max_pred > CN_MAX_PRED || min_pred < 0) {
+    cn_set_error("decode: beam=%d (1..%d) max_pred=%d (1..%d) min_pred=%d unsupported", beam, CN_MAX_BEAM, max_pred,
+                 CN_MAX_PRED, min_pred);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_model(ctx, "decode", max_pred, min_pred, "decode: max_pred exceeds positional table"));
+  CN_TRY(dec_check_workspace("decode", workspace_bytes, conette_decode_workspace_bytes(ctx, batch, t_audio, beam, max_pred)));
+  DecArgs a;
+  memset(&a, 0, sizeof(a));  // (padding included: the record is the graph key)
+  a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.bos_ids = bos_ids, a.forbid = forbid_mask;
+  a.best_preds = best_preds, a.best_lprobs = best_lprobs, a.mult_preds = mult_preds, a.mult_lprobs = mult_lprobs;
+  a.out_sizes = out_sizes, a.step0_logits = step0_logits, a.trace_sel = trace_sel, a.trace_val = trace_val;
+  a.margins = margins, a.ws = (char*)workspace;
+  a.B = batch, a.Ta = t_audio, a.beam = beam, a.min_pred = min_pred, a.maxp = max_pred;
+  hipStream_t s = (hipStream_t)stream;
+  return dec_graph_run(ctx, a, s, [&]() -> int { CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, s)); });
 }
 
 extern "C" int32_t conette_decode_graph_nodes(const conette_ctx* ctx) {
@@ -1489,85 +1519,21 @@ static int forcing_prefill_impl(conette_ctx* ctx, const float* frame_embs, const
                                 int B, int Ta, int cpa, int cap_len, float* logits, const CnScoreOut* score, char* wsp,
                                 hipStream_t s) {
   const conette_config& cfg = ctx->cfg;
-  const int d = cfg.d_model, NL = cfg.n_layers, R = B * cpa * cap_len, V = cfg.vocab_size, dff = cfg.d_ff;
+  const int d = cfg.d_model, NL = cfg.n_layers, R = B * cpa * cap_len, V = cfg.vocab_size;
   DecWs w = dec_ws(ctx, B, Ta, cpa * cap_len, 1, wsp, score != nullptr);  // rows = B * cpa * cap_len ("beam" = cpa * cap_len, one step)
-  T* fe_t = (T*)w.fe_t;
-  T* mem = (T*)w.mem;
-  T* kvc = (T*)w.kvc;
   T* xt = (T*)w.xt;
-  T* attn_t = (T*)w.attn_t;
-  T* ffh = (T*)w.ffh;
-  const int kv_ld = NL * 2 * d;
   const float scale = 1.0f / sqrtf((float)(d / cfg.nhead));
   const int rblocks = cn_cdiv(R, 4);
-  {
-    CnProfScope ps(ctx, CONETTE_PROF_DEC_PREPARE, s);
-    const size_t n = (size_t)B * Ta * CN_FEAT;
-    hipLaunchKernelGGL((cn_cvt_kernel<T>), dim3((unsigned)((n + 1023) / 1024 < 4096 ? (n + 1023) / 1024 : 4096)), dim3(256), 0, s,
-                       frame_embs, fe_t, n);
-    CN_LAUNCH_CHECK();
-    EpiBiasAct<T, ACT_RELU> ep{ctx->proj_b, mem, d, ACT_RELU};
-    CN_TRY(cn_mm(fe_t, CN_FEAT, (const T*)ctx->proj_w, CN_FEAT, B * Ta, d, CN_FEAT, ep, s));
-    EpiBiasAct<T, ACT_NONE> ekv{ctx->kv_b, kvc, kv_ld, ACT_NONE};
-    CN_TRY(cn_mm(mem, d, (const T*)ctx->kv_w, d, B * Ta, kv_ld, d, ekv, s));
-  }
+  CN_TRY(dec_prepare<T>(ctx, frame_embs, B, Ta, w, s));
   hipLaunchKernelGGL((cn_embed_caps_kernel<T>), dim3(rblocks), dim3(256), 0, s, caps, ctx->emb, ctx->pe, cap_len, R,
                      sqrtf((float)d), w.x, xt);
   CN_LAUNCH_CHECK();
-  for (int l = 0; l < NL; ++l) {
-    const CnLayerW& lw = ctx->layers[l];
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-      EpiBiasAct<float, ACT_NONE> eq{lw.sa_in_b, w.qkv, 3 * d, ACT_NONE};
-      CN_TRY(cn_mm(xt, d, (const T*)lw.sa_in_w, d, R, 3 * d, d, eq, s));
-    }
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
-      hipLaunchKernelGGL((cn_self_attn_causal_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.qkv, caps, cap_len, R, cfg.pad_id,
-                         scale, attn_t);
-      CN_LAUNCH_CHECK();
-    }
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-      EpiResid eo{lw.sa_out_b, nullptr, w.x, w.tmp, d};
-      CN_TRY(cn_mm(attn_t, d, (const T*)lw.sa_out_w, d, R, d, d, eo, s));
-    }
-    hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.tmp, 1, (size_t)0, (const float*)nullptr,
-                       (const float*)nullptr, lw.n1w, lw.n1b, R, w.x, xt);
-    CN_LAUNCH_CHECK();
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-      EpiBiasAct<float, ACT_NONE> ecq{lw.ca_q_b, w.q, d, ACT_NONE};
-      CN_TRY(cn_mm(xt, d, (const T*)lw.ca_q_w, d, R, d, d, ecq, s));
-    }
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
-      hipLaunchKernelGGL((cn_cross_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, kvc, kv_ld, l * 2 * d, frame_lens, R,
-                         cpa * cap_len, Ta, scale, attn_t);
-      CN_LAUNCH_CHECK();
-    }
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-      EpiResid eco{lw.ca_out_b, nullptr, w.x, w.tmp, d};
-      CN_TRY(cn_mm(attn_t, d, (const T*)lw.ca_out_w, d, R, d, d, eco, s));
-    }
-    hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.tmp, 1, (size_t)0, (const float*)nullptr,
-                       (const float*)nullptr, lw.n2w, lw.n2b, R, w.x, xt);
-    CN_LAUNCH_CHECK();
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-      EpiBiasAct<T, CnGeluAct<T>::value> e1{lw.ff1_b, ffh, dff, CnGeluAct<T>::value};
-      CN_TRY(cn_mm(xt, d, (const T*)lw.ff1_w, d, R, dff, d, e1, s));
-    }
-    {
-      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-      EpiResid e2{lw.ff2_b, nullptr, w.x, w.tmp, d};
-      CN_TRY(cn_mm(ffh, dff, (const T*)lw.ff2_w, dff, R, d, dff, e2, s));
-    }
-    hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.tmp, 1, (size_t)0, (const float*)nullptr,
-                       (const float*)nullptr, lw.n3w, lw.n3b, R, w.x, xt);
-    CN_LAUNCH_CHECK();
-  }
+  auto self_attn = [&](int) {
+    hipLaunchKernelGGL((cn_self_attn_causal_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.qkv, caps, cap_len, R, cfg.pad_id,
+                       scale, (T*)w.attn_t);
+  };
+  // (ffn2_split = false at every precision: FFN2 as one GEMM is the summation order the outputs of this pass are defined by)
+  for (int l = 0; l < NL; ++l) CN_TRY((dec_sublayer_layer<T>(ctx, w, l, frame_lens, R, Ta, cpa * cap_len, false, self_attn, s)));
   CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
   if (score) {  // no logits: every row's log-probability of its target, summed per caption (dec_score.h)
     const int S = cn_score_slabs(R, V, ctx->n_cu, ctx->score_vsplit);
@@ -1597,19 +1563,8 @@ extern "C" int conette_forcing(conette_ctx* ctx, const float* frame_embs, const 
     cn_set_error("forcing: bad argument");
     return CN_ERR_ARG;
   }
-  if (cap_len < 1 || cap_len > CN_MAX_PRED || cap_len > ctx->pe_len) {
-    cn_set_error("forcing: cap_len=%d unsupported (1..%d)", cap_len, CN_MAX_PRED);
-    return CN_ERR_ARG;
-  }
-  if (ctx->cfg.d_model != 256 || ctx->cfg.nhead != 8) {
-    cn_set_error("forcing: kernels are specialised for d_model=256, nhead=8");
-    return CN_ERR_ARG;
-  }
-  const size_t need = conette_forcing_workspace_bytes(ctx, batch, t_audio, cap_len);
-  if (workspace_bytes < need) {
-    cn_set_error("forcing: workspace %zu < %zu", workspace_bytes, need);
-    return CN_ERR_WORKSPACE;
-  }
+  CN_TRY(dec_check_model(ctx, "forcing", cap_len, 0, "forcing: cap_len=%d unsupported (1..%d)", cap_len, CN_MAX_PRED));
+  CN_TRY(dec_check_workspace("forcing", workspace_bytes, conette_forcing_workspace_bytes(ctx, batch, t_audio, cap_len)));
   hipStream_t s = (hipStream_t)stream;
   if (!ctx->forcing_stepwise) {  // default: one causal pass over all caption positions
     CN_BY_PRECISION(ctx, forcing_prefill_impl<OT>(ctx, frame_embs, frame_lens, caps_in, batch, t_audio, 1, cap_len, logits,
@@ -1618,15 +1573,15 @@ extern "C" int conette_forcing(conette_ctx* ctx, const float* frame_embs, const 
   // CONETTE_OPT_FORCING_STEPWISE: the KV-cached step kernels fed with the caption (cross-check of the pass above)
   // outputs of the search bookkeeping that a forced pass does not produce: parked in the workspace tail
   char* tail = (char*)workspace + conette_decode_workspace_bytes(ctx, batch, t_audio, 1, cap_len);
-  int32_t* mult_preds = (int32_t*)tail;
-  float* mult_lprobs = (float*)(tail + cn_align((size_t)batch * cap_len * 4));
-  tail += cn_align((size_t)batch * cap_len * 8);
-  int32_t* sizes = (int32_t*)tail;
-  int32_t* bos = sizes + 2;  // init kernel input; any valid ids: column 0 of the captions
-  (void)bos;
-  CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, frame_embs, frame_lens, caps_in, nullptr, batch, t_audio, 1, 0, cap_len, mult_preds,
-                               mult_lprobs, mult_preds, mult_lprobs, sizes, nullptr, nullptr, nullptr, (char*)workspace, s,
-                               caps_in, logits));
+  DecArgs a = {};
+  a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.ws = (char*)workspace;
+  a.bos_ids = caps_in;  // init kernel input; any valid ids
+  a.B = batch, a.Ta = t_audio, a.beam = 1, a.min_pred = 0, a.maxp = cap_len;
+  a.mult_preds = a.best_preds = (int32_t*)tail;
+  a.mult_lprobs = a.best_lprobs = (float*)(tail + cn_align((size_t)batch * cap_len * 4));
+  a.out_sizes = (int32_t*)(tail + cn_align((size_t)batch * cap_len * 8));
+  a.force_caps = caps_in, a.force_logits = logits;
+  CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, s));
 }
 
 extern "C" size_t conette_score_workspace_bytes(const conette_ctx* ctx, int32_t n_audio, int32_t t_audio,
@@ -1648,16 +1603,9 @@ extern "C" int conette_score(conette_ctx* ctx, const float* frame_embs, const in
     cn_set_error("score: bad argument");
     return CN_ERR_ARG;
   }
-  if (cap_len < 1 || cap_len > CN_MAX_PRED || cap_len > ctx->pe_len) {
-    cn_set_error("score: cap_len=%d unsupported (1..%d)", cap_len, CN_MAX_PRED);
-    return CN_ERR_ARG;
-  }
+  CN_TRY(dec_check_model(ctx, "score", cap_len, 0, "score: cap_len=%d unsupported (1..%d)", cap_len, CN_MAX_PRED));
   if (caps_per_audio < 1) {
     cn_set_error("score: caps_per_audio=%d < 1", caps_per_audio);
-    return CN_ERR_ARG;
-  }
-  if (ctx->cfg.d_model != 256 || ctx->cfg.nhead != 8) {
-    cn_set_error("score: kernels are specialised for d_model=256, nhead=8");
     return CN_ERR_ARG;
   }
   const size_t need = conette_score_workspace_bytes(ctx, n_audio, t_audio, caps_per_audio, cap_len);
@@ -1665,10 +1613,7 @@ extern "C" int conette_score(conette_ctx* ctx, const float* frame_embs, const in
     cn_set_error("score: %d x %d x %d rows in one call are too many (split the call)", n_audio, caps_per_audio, cap_len);
     return CN_ERR_ARG;
   }
-  if (workspace_bytes < need) {
-    cn_set_error("score: workspace %zu < %zu", workspace_bytes, need);
-    return CN_ERR_WORKSPACE;
-  }
+  CN_TRY(dec_check_workspace("score", workspace_bytes, need));
   const CnScoreOut out{targets, tok_lprobs, sum_lprobs, n_tokens};
   CN_BY_PRECISION(ctx, forcing_prefill_impl<OT>(ctx, frame_embs, frame_lens, caps_in, n_audio, t_audio, caps_per_audio, cap_len,
                                                 nullptr, &out, (char*)workspace, (hipStream_t)stream));
@@ -1683,28 +1628,18 @@ extern "C" int conette_greedy(conette_ctx* ctx, const float* frame_embs, const i
     cn_set_error("greedy: bad argument");
     return CN_ERR_ARG;
   }
-  if (max_pred < 1 || max_pred > CN_MAX_PRED || max_pred > ctx->pe_len || min_pred < 0) {
-    cn_set_error("greedy: max_pred=%d (1..%d) min_pred=%d unsupported", max_pred, CN_MAX_PRED, min_pred);
-    return CN_ERR_ARG;
-  }
-  if (ctx->cfg.d_model != 256 || ctx->cfg.nhead != 8) {
-    cn_set_error("greedy: kernels are specialised for d_model=256, nhead=8");
-    return CN_ERR_ARG;
-  }
-  const size_t base = conette_decode_workspace_bytes(ctx, batch, t_audio, 1, max_pred);
-  const size_t need = base + cn_align((size_t)batch * max_pred * 4) + 2 * cn_align((size_t)batch * 4);
-  if (workspace_bytes < need) {
-    cn_set_error("greedy: workspace %zu < %zu", workspace_bytes, need);
-    return CN_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  char* tail = (char*)workspace + base;
-  int32_t* mult_preds = (int32_t*)tail;  // beam 1: the single hypothesis of every clip
-  float* mult_lprobs = (float*)(tail + cn_align((size_t)batch * max_pred * 4));
-  float* best_lprobs = (float*)(tail + cn_align((size_t)batch * max_pred * 4) + cn_align((size_t)batch * 4));
-  CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, frame_embs, frame_lens, bos_ids, forbid_mask, batch, t_audio, 1, min_pred, max_pred, preds,
-                               best_lprobs, mult_preds, mult_lprobs, out_sizes, nullptr, nullptr, nullptr, (char*)workspace,
-                               s, nullptr, nullptr, logits));
+  CN_TRY(dec_check_model(ctx, "greedy", max_pred, min_pred, "greedy: max_pred=%d (1..%d) min_pred=%d unsupported", max_pred, CN_MAX_PRED,
+                         min_pred));
+  CN_TRY(dec_check_workspace("greedy", workspace_bytes, conette_greedy_workspace_bytes(ctx, batch, t_audio, max_pred)));
+  char* tail = (char*)workspace + conette_decode_workspace_bytes(ctx, batch, t_audio, 1, max_pred);
+  DecArgs a = {};
+  a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.bos_ids = bos_ids, a.forbid = forbid_mask, a.ws = (char*)workspace;
+  a.B = batch, a.Ta = t_audio, a.beam = 1, a.min_pred = min_pred, a.maxp = max_pred;
+  a.best_preds = preds, a.out_sizes = out_sizes, a.greedy_logits = logits;
+  a.mult_preds = (int32_t*)tail;  // beam 1: the single hypothesis of every clip
+  a.mult_lprobs = (float*)(tail + cn_align((size_t)batch * max_pred * 4));
+  a.best_lprobs = (float*)(tail + cn_align((size_t)batch * max_pred * 4) + cn_align((size_t)batch * 4));
+  CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
 }
 
 extern "C" size_t conette_greedy_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t max_pred) {
