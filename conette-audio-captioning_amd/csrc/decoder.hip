@@ -809,6 +809,8 @@ __global__ __launch_bounds__(256) void cn_greedy_logits_kernel(const float* __re
   }
 }
 
+#include "dec_sample.h"
+
 struct DecWs {
   void *fe_t, *mem, *kvc, *xt, *attn_t, *ffh, *kc, *vc;
   float *x, *x2, *qkv, *q, *tmp, *logits, *slabs;
@@ -888,6 +890,12 @@ struct DecArgs {
   const int32_t* force_caps;  // teacher forcing: beam == 1, maxp == caption length, no search
   float* force_logits;
   float* greedy_logits;  // conette_greedy: the masked logits of every step
+  const float* uniforms;  // conette_sample: beam == samples per clip, mult_preds / mult_lprobs == preds / sum_lprobs (dec_sample.h)
+  int32_t* sample_lens;
+  float* sample_tok_lp;       // these two are optional
+  float* sample_step_logits;
+  float temperature, top_p;
+  int top_k;
   bool operator==(const DecArgs& o) const { return memcmp(this, &o, sizeof(DecArgs)) == 0; }
 };
 
@@ -1011,6 +1019,7 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
   const int d = cfg.d_model, NL = cfg.n_layers, R = B * beam, V = cfg.vocab_size, dff = cfg.d_ff;
   DecWs w = dec_ws(ctx, B, Ta, beam, maxp, a.ws);
   const bool forcing = a.force_caps != nullptr;
+  const bool sampling = a.uniforms != nullptr;
   const unsigned long long* kvalid = forcing ? w.kvalid : nullptr;
   T* kvc = (T*)w.kvc;
   T* xt = (T*)w.xt;
@@ -1027,6 +1036,11 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
   if (forcing) {
     hipLaunchKernelGGL(cn_force_init_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, a.force_caps, B, maxp, cfg.pad_id,
                        w.kvalid, w.anc);
+    CN_LAUNCH_CHECK();
+  }
+  if (sampling) {  // rows never change parents: every row is its own ancestor; w.slot holds the per-row finished flag
+    hipLaunchKernelGGL(cn_sample_init_kernel, dim3(64), dim3(256), 0, s, R, beam, maxp, w.anc, w.slot, a.sample_lens,
+                       a.sample_tok_lp);
     CN_LAUNCH_CHECK();
   }
 
@@ -1159,6 +1173,24 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
       CN_LAUNCH_CHECK();
     }
     CnProfScope ps_search(ctx, CONETTE_PROF_SEARCH, s);
+    if (sampling) {  // the per-row sampling step instead of the search step (dec_sample.h)
+      SmArgs sa;
+      sa.logits = w.logits, sa.forbid = a.forbid, sa.uniforms = a.uniforms, sa.prefix = w.prefix, sa.cur_tok = w.cur_tok;
+      sa.sum_lp = w.sum_lp, sa.fin = w.slot, sa.live = w.live, sa.preds = a.mult_preds, sa.sum_out = a.mult_lprobs;
+      sa.lens = a.sample_lens, sa.sizes = a.out_sizes, sa.tok_lp = a.sample_tok_lp, sa.step_logits = a.sample_step_logits;
+      sa.ldv = w.ldv, sa.V = V, sa.R = R, sa.maxp = maxp, sa.min_pred = min_pred, sa.eos_id = cfg.eos_id, sa.top_k = a.top_k;
+      sa.temperature = a.temperature, sa.top_p = a.top_p;
+      const int vpt = cn_cdiv(V, SM_T);
+#define SM_LAUNCH(VPT_) hipLaunchKernelGGL((cn_sample_step_kernel<VPT_>), dim3(R), dim3(SM_T), 0, s, sa, step)
+      if (vpt <= 2) SM_LAUNCH(2);
+      else if (vpt <= 4) SM_LAUNCH(4);
+      else if (vpt <= 6) SM_LAUNCH(6);
+      else if (vpt <= SM_VPT) SM_LAUNCH(8);
+      else SM_LAUNCH(0);  // vocabularies beyond 8192 entries: the logits are re-read from global memory
+#undef SM_LAUNCH
+      CN_LAUNCH_CHECK();
+      continue;
+    }
     if (V <= S3_T * S3_VPT && beam <= 8) {  // register-resident step (one block of 1024 threads per clip)
 #define S3_LAUNCH(NR_, VPT_)                                                                                          \
   hipLaunchKernelGGL((cn_search_step3_kernel<NR_, VPT_>), dim3(B), dim3(S3_T), 0, s, w.logits, w.ldv, V, beam, maxp,  \
@@ -1182,7 +1214,7 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
     }
     CN_LAUNCH_CHECK();
   }
-  if (forcing) return CN_OK;
+  if (forcing || sampling) return CN_OK;
   hipLaunchKernelGGL(cn_finalize_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, B, beam, maxp, cfg.eos_id, a.mult_preds,
                      a.mult_lprobs, w.out_len, a.best_preds, a.best_lprobs, w.eos_idx, a.out_sizes, a.margins);
   CN_LAUNCH_CHECK();
@@ -1639,6 +1671,58 @@ extern "C" int conette_greedy(conette_ctx* ctx, const float* frame_embs, const i
   a.mult_preds = (int32_t*)tail;  // beam 1: the single hypothesis of every clip
   a.mult_lprobs = (float*)(tail + cn_align((size_t)batch * max_pred * 4));
   a.best_lprobs = (float*)(tail + cn_align((size_t)batch * max_pred * 4) + cn_align((size_t)batch * 4));
+  CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
+}
+
+// ---- sampling (dec_sample.h): the step path with the per-row sampling decision in place of the search step ----
+extern "C" size_t conette_sample_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t n_samples,
+                                                 int32_t max_pred) {
+  if (!ctx || batch <= 0 || t_audio <= 0 || n_samples <= 0 || max_pred <= 0) return 0;
+  return conette_decode_workspace_bytes(ctx, batch, t_audio, n_samples, max_pred);
+}
+
+extern "C" int conette_sample(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                              const uint8_t* forbid_mask, const float* uniforms, int32_t batch, int32_t t_audio,
+                              int32_t n_samples, int32_t min_pred, int32_t max_pred, float temperature, int32_t top_k,
+                              float top_p, int32_t* preds, float* sum_lprobs, int32_t* lens, int32_t* out_sizes,
+                              float* tok_lprobs, float* step_logits, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ctx || !frame_embs || !frame_lens || !bos_ids || !uniforms || !preds || !sum_lprobs || !lens || !out_sizes || !workspace ||
+      batch <= 0 || t_audio <= 0) {
+    cn_set_error("sample: bad argument");
+    return CN_ERR_ARG;
+  }
+  if (n_samples < 1 || n_samples > CN_MAX_BEAM) {
+    cn_set_error("sample: n_samples=%d unsupported (1..%d)", n_samples, CN_MAX_BEAM);
+    return CN_ERR_ARG;
+  }
+  if (!(temperature > 0.f) || !(temperature < INFINITY)) {
+    cn_set_error("sample: temperature=%g must be finite and > 0", (double)temperature);
+    return CN_ERR_ARG;
+  }
+  if (top_k < 0) {
+    cn_set_error("sample: top_k=%d < 0", top_k);
+    return CN_ERR_ARG;
+  }
+  if (!(top_p > 0.f) || !(top_p <= 1.f)) {
+    cn_set_error("sample: top_p=%g outside (0, 1]", (double)top_p);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_model(ctx, "sample", max_pred, min_pred, "sample: max_pred=%d (1..%d) min_pred=%d unsupported", max_pred,
+                         CN_MAX_PRED, min_pred));
+  if (ctx->cfg.vocab_size > SM_T * SM_MAX_SLABS) {
+    cn_set_error("sample: vocab_size=%d unsupported (at most %d)", ctx->cfg.vocab_size, SM_T * SM_MAX_SLABS);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_workspace("sample", workspace_bytes, conette_sample_workspace_bytes(ctx, batch, t_audio, n_samples, max_pred)));
+  DecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.bos_ids = bos_ids, a.forbid = forbid_mask, a.ws = (char*)workspace;
+  a.B = batch, a.Ta = t_audio, a.beam = n_samples, a.min_pred = min_pred, a.maxp = max_pred;
+  a.mult_preds = preds, a.mult_lprobs = sum_lprobs, a.out_sizes = out_sizes;
+  a.uniforms = uniforms, a.sample_lens = lens, a.sample_tok_lp = tok_lprobs, a.sample_step_logits = step_logits;
+  a.temperature = temperature, a.top_p = top_p, a.top_k = top_k;
+  // (eager: the caller's output buffers usually change from call to call, which a graph cache keyed on them would only churn
+  //  through; the launch sequence is static and holds no host state, so the caller may capture it)
   CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
 }
 

@@ -32,7 +32,7 @@ EXPORTS = (
     "conette_set_option", "conette_profile_enable", "conette_profile_read", "conette_stream_create_masked",
     "conette_stream_destroy", "conette_forcing_workspace_bytes", "conette_forcing",
     "conette_greedy_workspace_bytes", "conette_greedy", "conette_decode_graph_nodes", "conette_encode_nonfinite",
-    "conette_score_workspace_bytes", "conette_score",
+    "conette_score_workspace_bytes", "conette_score", "conette_sample_workspace_bytes", "conette_sample",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -141,6 +141,12 @@ def load_library() -> C.CDLL:
     lib.conette_score.restype = C.c_int
     lib.conette_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_sample_workspace_bytes.restype = C.c_size_t
+    lib.conette_sample_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_sample.restype = C.c_int
+    lib.conette_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.conette_greedy_workspace_bytes.restype = C.c_size_t
     lib.conette_greedy_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.conette_greedy.restype = C.c_int
@@ -643,6 +649,58 @@ class Engine:
         _check(st, "conette_greedy")
         ps = int(sizes[0].item())
         return {"logits": logits[:, :ps].contiguous(), "preds": preds[:, :ps].contiguous()}
+
+    def sample(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, bos_ids: torch.Tensor,
+               forbid_mask: Optional[torch.Tensor], n_samples: int, min_pred: int, max_pred: int, temperature: float = 1.0,
+               top_k: int = 0, top_p: float = 1.0, uniforms: Optional[torch.Tensor] = None,
+               generator: Optional[torch.Generator] = None, want_tokens: bool = False,
+               want_logits: bool = False) -> Dict[str, torch.Tensor]:
+        """``n_samples`` captions per clip drawn from the model's distribution (conette_sample, include/conette_hip.h; the rule:
+        sampling.py): {"preds": (B, n, max_pred) int32 with pad_id after the end, "sum_lprobs": (B, n), "lens": (B, n) int32,
+        "sizes": (2,) int32 [, "tok_lprobs": (B, n, max_pred)] [, "step_logits": (B, n, max_pred, vocab), the raw logits each
+        decision saw]}.  ``uniforms`` (max_pred, B, n) fp32 in [0, 1) are drawn with ``torch.rand(..., generator=generator)`` on
+        the device when none are passed; more than 16 samples per clip run as several calls (sampling.plan_sample_chunks), sample
+        j reading column j of the uniforms."""
+        from . import sampling
+        b, t, _ = frame_embs.shape
+        n, max_pred = int(n_samples), int(max_pred)
+        plan = sampling.plan_sample_chunks(n)
+        if uniforms is None:
+            uniforms = torch.rand((max_pred, b, n), dtype=torch.float32, device=self.device, generator=generator)
+        if tuple(uniforms.shape) != (max_pred, b, n):
+            raise ValueError(f"sample: uniforms {tuple(uniforms.shape)} are not (max_pred, batch, n_samples) = {(max_pred, b, n)}")
+        uni = uniforms.to(self.device, torch.float32)
+        fe = frame_embs.to(self.device, torch.float32).contiguous()
+        lens_in = frame_lens.to(self.device, torch.int32).contiguous()
+        bos = bos_ids.to(self.device, torch.int32).contiguous()
+        fm = None
+        if forbid_mask is not None:
+            if forbid_mask.numel() != self.vocab_size:
+                raise ValueError("forbid_mask must have vocab_size entries")
+            fm = forbid_mask.to(self.device, torch.uint8).contiguous()
+        ctx = self._ctx_dec
+        parts = []
+        for first, cnt in plan:
+            e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+            o = {"preds": e((b, cnt, max_pred), torch.int32), "sum_lprobs": e((b, cnt), torch.float32),
+                 "lens": e((b, cnt), torch.int32), "sizes": e((2,), torch.int32),
+                 "tok_lprobs": e((b, cnt, max_pred), torch.float32) if want_tokens else None,
+                 "step_logits": e((b, cnt, max_pred, self.vocab_size), torch.float32) if want_logits else None}
+            u = uni[:, :, first:first + cnt].contiguous()
+            need = self.lib.conette_sample_workspace_bytes(ctx, b, t, cnt, max_pred)
+            wsb = self._workspace("dec", need)
+            st = self.lib.conette_sample(ctx, _ptr(fe), _ptr(lens_in), _ptr(bos), _ptr(fm), _ptr(u), b, t, cnt, int(min_pred),
+                                         max_pred, float(temperature), int(top_k), float(top_p), _ptr(o["preds"]),
+                                         _ptr(o["sum_lprobs"]), _ptr(o["lens"]), _ptr(o["sizes"]), _ptr(o["tok_lprobs"]),
+                                         _ptr(o["step_logits"]), _ptr(wsb), wsb.numel(), _stream())
+            _check(st, "conette_sample")
+            parts.append(o)
+        if len(parts) == 1:
+            return {k: v for k, v in parts[0].items() if v is not None}
+        out = {k: torch.cat([p[k] for p in parts], dim=1) for k in ("preds", "sum_lprobs", "lens", "tok_lprobs", "step_logits")
+               if parts[0][k] is not None}
+        out["sizes"] = torch.stack([p["sizes"] for p in parts]).amax(dim=0)
+        return out
 
     def decode_input_buffer(self, b: int, t: int, beam: int, max_pred: int, slot: int = 0, margins: bool = False,
                             exact: bool = False) -> torch.Tensor:

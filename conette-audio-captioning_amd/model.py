@@ -271,6 +271,29 @@ class CoNeTTEModel:
             raise ValueError(f"Invalid task mode {mode} for batch_to_task_token_ids.")
         return self.task_id_to_token_id[torch.as_tensor(idx, dtype=torch.long)]
 
+    def _split_tasks(self, task: Union[str, List[str], None], bsize: int):
+        """(tasks, datasets, sources) of a batch, with forward's errors (model.py:215-238)."""
+        if task is None:
+            tasks = [self.default_task] * bsize
+        elif isinstance(task, str):
+            tasks = [task] * bsize
+        elif len(task) != bsize:
+            raise ValueError(f"Invalid number of tasks with input. (found {len(task)} tasks but {bsize} elements)")
+        else:
+            tasks = task
+        del task
+        for task in tasks:
+            if task not in self.config.task_names:
+                raise ValueError(f"Invalid argument {tasks=}. (task {task} is not in {self.config.task_names})")
+        dataset_lst = [self.default_task] * bsize
+        source_lst: List[Optional[str]] = [None] * bsize
+        for i, task in enumerate(tasks):
+            parts = task.split("_")
+            dataset_lst[i] = parts[0]
+            if len(parts) >= 2:
+                source_lst[i] = "_".join(parts[1:])
+        return tasks, dataset_lst, source_lst
+
     # ---- forward (model.py:185-261) -----------------------------------------------------------------
     @torch.no_grad()
     def forward(self, x: Union[Tensor, str, Iterable[str], Iterable[Tensor]],
@@ -291,25 +314,7 @@ class CoNeTTEModel:
             wave = batch.pop("_wave", None)
 
             bsize = len(batch["audio"])
-            if task is None:
-                tasks = [self.default_task] * bsize
-            elif isinstance(task, str):
-                tasks = [task] * bsize
-            elif len(task) != bsize:
-                raise ValueError(f"Invalid number of tasks with input. (found {len(task)} tasks but {bsize} elements)")
-            else:
-                tasks = task
-            del task
-            for task in tasks:
-                if task not in self.config.task_names:
-                    raise ValueError(f"Invalid argument {tasks=}. (task {task} is not in {self.config.task_names})")
-            dataset_lst = [self.default_task] * bsize
-            source_lst: List[Optional[str]] = [None] * bsize
-            for i, task in enumerate(tasks):
-                parts = task.split("_")
-                dataset_lst[i] = parts[0]
-                if len(parts) >= 2:
-                    source_lst[i] = "_".join(parts[1:])
+            tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
 
             overflow = False
             if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
@@ -340,6 +345,68 @@ class CoNeTTEModel:
         return self.forward(x=x, sr=sr, x_shapes=x_shapes, preprocess=preprocess, threshold=threshold, task=task,
                             beam_size=beam_size, min_pred_size=min_pred_size, max_pred_size=max_pred_size,
                             forbid_rep_mode=forbid_rep_mode)
+
+    @torch.no_grad()
+    def sample(self, x, num_samples: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+               seed: Optional[int] = None, generator: Optional[torch.Generator] = None, sr=None, x_shapes=None,
+               preprocess: bool = True, task: Union[str, List[str], None] = None, min_pred_size: Optional[int] = None,
+               max_pred_size: Optional[int] = None, forbid_rep_mode: Optional[str] = None) -> Dict[str, Any]:
+        """``num_samples`` captions per clip DRAWN from the model's distribution (temperature, top-k and nucleus sampling on the
+        device: conette_sample; the rule: sampling.py) instead of searched for.  ``x``, ``task`` and the size / mask arguments as
+        in ``forward``, whose keys it returns: "mult_preds" (B, n, pred_size), "mult_cands", "mult_lprobs" (B, n) -- the mean
+        log-probability per token, sum / length, as the beam search reports it --, "preds" / "cands" / "lprobs": per clip the
+        sample with the highest mean log-probability; plus "sum_lprobs" (B, n), "lens" (B, n) and "tasks" (and the tags, when it
+        ran the preprocessor).  The log-probabilities are the model's own (temperature 1, unfiltered), whatever the sampling
+        settings.  ``seed`` (or a device ``generator``) makes the draw reproducible; precision "certified" samples through its
+        16-bit base context, like ``teacher_forcing`` and ``score_captions``.  With waveforms in, an overflow of the 16-bit
+        encoders' fp16 residual stream raises as in ``forward`` (every precision here: there is no exact re-run of a draw)."""
+        n = int(num_samples)
+        if n < 1:
+            raise ValueError(f"Invalid argument num_samples={num_samples}. (expected at least 1)")
+        with torch.cuda.device(self.device):
+            if preprocess:
+                batch = self.preprocessor(x, sr, x_shapes)
+                clip_probs = batch.pop("clip_probs")
+            elif isinstance(x, dict):
+                batch, clip_probs = {"audio": x["audio"], "audio_shape": torch.as_tensor(x["audio_shape"])}, None
+            else:
+                assert isinstance(x, Tensor) and isinstance(x_shapes, Tensor)
+                batch, clip_probs = {"audio": x.to(self.device), "audio_shape": x_shapes.to(self.device)}, None
+            audio, audio_shape = batch["audio"], batch["audio_shape"]
+            if audio.ndim == 4:
+                audio = audio.squeeze(dim=1)
+            bsize = len(audio)
+            tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
+            if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
+                bad = self.engine.encode_nonfinite()       # (include/conette_hip.h: conette_encode_nonfinite)
+                if bad:
+                    raise RuntimeError(
+                        f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
+                        "positions with non-finite LayerNorm statistics); sample with precision='exact' or 'fp32' for this checkpoint")
+            cfg = self.config
+            min_pred = cfg.min_pred_size if min_pred_size is None else int(min_pred_size)
+            max_pred = cfg.max_pred_size if max_pred_size is None else int(max_pred_size)
+            if seed is not None:
+                generator = torch.Generator(device=self.device).manual_seed(int(seed))
+            res = self.engine.sample(audio, audio_shape[:, 1].to(torch.int32), self.batch_to_task_token_ids(dataset_lst, source_lst),
+                                     self.get_forbid_rep_mask(forbid_rep_mode), n, min_pred, max_pred, temperature=temperature,
+                                     top_k=top_k, top_p=top_p, generator=generator)
+            lens = res["lens"]
+            mult_lprobs = res["sum_lprobs"] / lens.to(torch.float32)
+            best = mult_lprobs.argmax(dim=1)                                        # (the first maximum, like beam.py:214-217)
+            rows = torch.arange(bsize, device=best.device)
+            pred_size, best_maxlen = (int(v) for v in torch.stack([res["sizes"][0], lens[rows, best].max()]).tolist())  # the one host sync
+            mult_preds = res["preds"][:, :, :pred_size].to(torch.long).contiguous()
+            preds = mult_preds[rows, best][:, :best_maxlen].contiguous()
+            outs = {
+                "cands": self.tokenizer.decode_rec(preds), "preds": preds, "lprobs": mult_lprobs[rows, best],
+                "mult_cands": self.tokenizer.decode_rec(mult_preds), "mult_preds": mult_preds, "mult_lprobs": mult_lprobs,
+                "sum_lprobs": res["sum_lprobs"], "lens": lens, "tasks": tasks,
+            }
+            if clip_probs is not None:
+                outs["tags_probs"] = clip_probs
+                outs["tags"] = probs_to_names(clip_probs, 0.3, self.audioset_idx_to_name)
+            return outs
 
     def teacher_forcing(self, x, caps_in: Tensor, sr=None, x_shapes=None, preprocess: bool = True) -> Tensor:
         """CoNeTTEPLM.decode_audio(encode_audio(...), "forcing", caps_in=caps_in) (pl_modules/conette.py:392-417,
@@ -450,13 +517,14 @@ class CoNeTTEModel:
         """The decode_audio surface shared by CoNeTTEPLM (pl_modules/conette.py:386-450) and BaselinePLM
         (pl_modules/baseline.py:339-401): ``encoder_outs`` = the preprocessor's output ({"audio": (B, T, 768),
         "audio_shape": (B, 2)}; the projection of conette.py:457 / baseline.py:409 runs inside the engine),
-        ``decode_method`` in ("forcing", "greedy", "generate").
+        ``decode_method`` in ("forcing", "greedy", "generate", "sample").
 
         * "forcing": ``caps_in`` required -> logits (B, vocab, cap_len)
         * "greedy": kwargs bos_id (default <bos>: BaselinePLM has no task token), min_pred_size, max_pred_size,
           forbid_rep_mode -> logits (B, vocab, pred_size)
         * "generate": kwargs bos_id (int or (B,) tensor; REQUIRED for CoNeTTE-style task prompting, default <bos>),
-          beam_size, min_pred_size, max_pred_size, forbid_rep_mode -> (preds, lprobs, mult_preds, mult_lprobs)"""
+          beam_size, min_pred_size, max_pred_size, forbid_rep_mode -> (preds, lprobs, mult_preds, mult_lprobs)
+        * "sample": the keyword arguments of ``sample`` (num_samples, temperature, top_k, top_p, seed, task ...) -> its dict"""
         if decode_method == "forcing":
             if "caps_in" not in kwargs:
                 raise ValueError(f"Please provide a 'caps_in' keyword argument with {decode_method=}. "
@@ -466,6 +534,8 @@ class CoNeTTEModel:
             return self.greedy_search(encoder_outs, preprocess=False, bos_id=kwargs.get("bos_id"),
                                       min_pred_size=kwargs.get("min_pred_size"), max_pred_size=kwargs.get("max_pred_size"),
                                       forbid_rep_mode=kwargs.get("forbid_rep_mode"))
+        if decode_method == "sample":   # kwargs of CoNeTTEModel.sample -> its dict
+            return self.sample(encoder_outs, preprocess=False, **kwargs)
         if decode_method == "generate":
             audio, audio_shape = encoder_outs["audio"], torch.as_tensor(encoder_outs["audio_shape"])
             if audio.ndim == 4:
@@ -490,7 +560,7 @@ class CoNeTTEModel:
             pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())
             return (res["best_preds"][:, :best_maxlen].to(torch.long).contiguous(), res["best_lprobs"],
                     res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous(), res["mult_lprobs"])
-        raise ValueError(f"Unknown argument {decode_method=}. (expected one of ('forcing', 'greedy', 'generate'))")
+        raise ValueError(f"Unknown argument {decode_method=}. (expected one of ('forcing', 'greedy', 'generate', 'sample'))")
 
     def _generate(self, audio: Tensor, audio_shape: Tensor, datasets: List[str], sources: List[Optional[str]], *,
                   beam_size=None, min_pred_size=None, max_pred_size=None, forbid_rep_mode=None,

@@ -3,6 +3,7 @@
 
     python -m conette_amd.predict --audio a.wav b.wav --task clotho --model_name DIR_OR_HUB_NAME \
         [--csv_export out.csv] [--precision certified|certified:BASE|bf16|bf16+f16dec|f16|mixed|mixed16|exact|fp32]
+        [--sample N --temperature T --top_k K --top_p P --seed S]
 
 ``--model_path`` (a Lightning training log directory with hydra/config.yaml + checkpoints/best.ckpt, predict.py:123-178) is
 accepted when the audio encoder's weights come with it: the reference builds its HF wrapper around the Lightning module and leaves
@@ -46,7 +47,12 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
                         help="With --model_path: a state dict of the ConvNeXt audio encoder (keys preprocessor.encoder.*, encoder.* or bare).")
     parser.add_argument("--device", type=str, help="Torch device used to run the model.", default="cuda_if_available")
     parser.add_argument("--token", type=_opt_str, help="Optional access token.", default=None)
-    parser.add_argument("--seed", type=_opt_int, help="Random seed value (inference is deterministic).", default=1234)
+    parser.add_argument("--seed", type=_opt_int, help="Random seed value (the search is deterministic; --sample draws with it).", default=1234)
+    parser.add_argument("--sample", type=int, default=0,
+                        help="N > 0: draw N captions per file from the model's distribution instead of searching (one row per draw).")
+    parser.add_argument("--temperature", type=float, help="With --sample: softmax temperature.", default=1.0)
+    parser.add_argument("--top_k", type=int, help="With --sample: keep the k most likely tokens (0: off).", default=0)
+    parser.add_argument("--top_p", type=float, help="With --sample: nucleus mass (1: off).", default=1.0)
     parser.add_argument("--csv_export", type=_opt_str, help="Path to CSV output file.", default=None)
     parser.add_argument("--verbose", type=int, help="Verbose level.", default=1)
     parser.add_argument("--precision", type=str, default=None,
@@ -148,8 +154,14 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
     tasks = args.task
     if tasks is not None and len(tasks) == 1:
         tasks = tasks[0]
-    outs = model(fpaths, task=tasks)
-    results = format_results(fpaths, outs["tasks"], outs["cands"])
+    if args.sample > 0:   # N draws per file, in the order drawn
+        outs = model.sample(fpaths, num_samples=args.sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                            seed=args.seed, task=tasks)
+        results = format_results([f for f in fpaths for _ in range(args.sample)], [t for t in outs["tasks"] for _ in range(args.sample)],
+                                 [c for cands in outs["mult_cands"] for c in cands])
+    else:
+        outs = model(fpaths, task=tasks)
+        results = format_results(fpaths, outs["tasks"], outs["cands"])
     for r in results:
         pylog.info(f"File '{r['audio']}' with task '{r['task']}':\n - '{r['candidate']}'")
     if args.csv_export is not None:

@@ -207,6 +207,40 @@ int conette_greedy(conette_ctx* ctx, const float* frame_embs, const int32_t* fra
                    float* logits, int32_t* preds, int32_t* out_sizes, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* Sampling: n_samples stochastic captions per clip from the model's distribution, on the KV-cached step path of conette_decode
+ * with a per-row sampling decision in place of the search step (csrc/dec_sample.h).  Rows r = clip * n_samples + sample never
+ * change parents.  One decision, from the row's logits z, its prefix, the step and a uniform u in [0, 1):
+ *   masks      z[eos] = -inf while step < min_pred; z[v] = -inf for every v with forbid_mask[v] set that occurs in the row's
+ *              prefix, the task token at position 0 included -- as conette_decode applies them
+ *   log-prob   log_softmax(masked z)[token], at temperature 1 and unfiltered: the quantity the beam search sums
+ *   top-k      with y = z / temperature, v is kept iff fewer than top_k tokens have a strictly larger y (0 or >= vocab: off)
+ *   top-p      with q = softmax(y over the top-k set), v is kept iff the total q of the tokens with strictly larger y is < top_p
+ *              (1: off).  Both rules are tie-inclusive and always keep the arg-max.  "Larger y" is decided on z (temperature > 0: the
+ *              same order in the reals), so two distinct logits never become a tie through the rounding of z / temperature.
+ *   draw       q renormalised over the kept set, walked in ascending token id: the first token whose running sum exceeds u, or
+ *              the largest kept id when rounding leaves the total <= u
+ * A row finishes when it draws <eos>, or at step max_pred - 1 (the drawn token stays).  A row without a finite logit takes <eos>,
+ * its log-prob becomes NaN, and it finishes.
+ *   uniforms    : dev (max_pred, batch * n_samples) fp32 in [0, 1), step-major; entries of finished rows are ignored.  The
+ *                 randomness is the caller's: the library holds no generator state
+ *   preds       : dev (batch, n_samples, max_pred) int32, pad_id after the end
+ *   sum_lprobs  : dev (batch, n_samples) fp32, the sum of the row's token log-probs in step order
+ *   lens        : dev (batch, n_samples) int32, tokens including <eos>
+ *   out_sizes   : dev (2) int32: [0] steps until every row had finished, [1] the longest caption
+ *   tok_lprobs  : optional dev (batch, n_samples, max_pred) fp32, 0 after the end; or NULL
+ *   step_logits : optional dev (batch * n_samples, max_pred, vocab) fp32, the RAW (unmasked) logits each decision saw; rows of
+ *                 steps after the row finished are unspecified; or NULL
+ * n_samples 1..16, max_pred <= 64, temperature finite and > 0, top_k >= 0, 0 < top_p <= 1, vocab <= 65536 (up to 8192 on the
+ * register-resident kernel, beyond on the generic one).  Asynchronous on `stream`, capturable, never replayed from the decode graph
+ * cache; results are bit-identical from run to run.  Works on decoder-only contexts and in every precision. */
+size_t conette_sample_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t n_samples,
+                                      int32_t max_pred);
+int conette_sample(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                   const uint8_t* forbid_mask, const float* uniforms, int32_t batch, int32_t t_audio, int32_t n_samples,
+                   int32_t min_pred, int32_t max_pred, float temperature, int32_t top_k, float top_p, int32_t* preds,
+                   float* sum_lprobs, int32_t* lens, int32_t* out_sizes, float* tok_lprobs, float* step_logits,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* a1: torchaudio.functional.resample (preprocessor.py:134-141), sinc_interpolation width 6,
  * rolloff 0.99.  in: dev (rows, n_in) fp32; out: dev (rows, n_out), n_out = ceil(n_in*new/orig). */
 int conette_resample(const float* in, int32_t rows, int32_t n_in, int32_t orig_sr, int32_t new_sr, float* out,
