@@ -151,6 +151,35 @@ class BaselinePLM:
         return {"lprobs": res["tok_lprobs"].reshape(b, n_caps, size - 1), "sum_lprobs": sums, "n_tokens": cnt,
                 "losses": losses, "loss": losses.mean()}
 
+    def align_captions(self, batch: Dict[str, Any], captions: Tensor, layers=None, per_layer: bool = False,
+                       mass: float = 0.5) -> Dict[str, Any]:
+        """``CoNeTTEModel.align_captions`` over precomputed frame embeddings, captions as in ``score_captions``: {"attn": (B,
+        n_caps, L - 1, T), "tokens", "lprobs", "sum_lprobs", "n_tokens", "peak_time", "mean_time", "span_time", "frame_sec"
+        [, "attn_layers"]} -- row t of a map belongs to the position that predicts token t + 1."""
+        from . import alignment, scoring
+        enc = self.encode_audio(batch["audio"], batch["audio_shape"])
+        captions = torch.as_tensor(captions)
+        if captions.is_floating_point() or captions.ndim not in (2, 3):
+            raise ValueError("captions must be an integer tensor of shape (bsize, caps_size) or (bsize, n_caps, caps_size).")
+        caps3 = captions[:, None] if captions.ndim == 2 else captions
+        b, n_caps, size = (int(v) for v in caps3.shape)
+        if b != enc["frame_embs"].shape[0]:
+            raise ValueError(f"Invalid number of captions {b} for {enc['frame_embs'].shape[0]} audio clips.")
+        caps_in, targets = scoring.split_captions(caps3.reshape(b * n_caps, size), self.pad_id)
+        res = self.engine.align(enc["frame_embs"], enc["frame_embs_lens"], caps_in, targets, caps_per_audio=n_caps, layers=layers,
+                                per_layer=per_layer)
+        t = int(enc["frame_embs"].shape[1])
+        attn = res["attn"].reshape(b, n_caps, size - 1, t)
+        tokens = targets.reshape(b, n_caps, size - 1).to(attn.device)
+        labelled = attn * tokens.ne(self.pad_id)[..., None]   # (a row that predicts a pad has no word to place: NaN times)
+        out = {"attn": attn, "tokens": tokens,
+               "lprobs": res["tok_lprobs"].reshape(b, n_caps, size - 1), "sum_lprobs": res["sum_lprobs"].reshape(b, n_caps),
+               "n_tokens": res["n_tokens"].reshape(b, n_caps), "frame_sec": alignment.FRAME_SEC,
+               **alignment.times(labelled, enc["frame_embs_lens"].to(attn.device), mass)}
+        if per_layer:
+            out["attn_layers"] = res["attn_layers"].reshape(-1, b, n_caps, size - 1, t)
+        return out
+
     def decode_audio(self, encoder_outs: Dict[str, Tensor], decode_method: str, **kwargs) -> Any:
         """baseline.py:339-401: "forcing" -> logits (B, vocab, cap_len); "greedy" -> the masked logits of every step
         (B, vocab, pred_size) (greedy.py:17-131); "generate" -> (preds, lprobs, mult_preds, mult_lprobs) (beam.py:22-227)."""

@@ -810,6 +810,7 @@ __global__ __launch_bounds__(256) void cn_greedy_logits_kernel(const float* __re
 }
 
 #include "dec_sample.h"
+#include "dec_align.h"
 
 struct DecWs {
   void *fe_t, *mem, *kvc, *xt, *attn_t, *ffh, *kc, *vc;
@@ -924,9 +925,12 @@ static int dec_prepare(conette_ctx* ctx, const float* frame_embs, int B, int Ta,
 //   rows_per_clip  consecutive rows that attend to one clip's audio memory (the "beam" of the cross-attention kernel)
 //   ffn2_split     FFN2 as split-K slabs summed by LN3 (16-bit and exact operands only: fp32 has no such GEMM) instead of one
 //                  GEMM with bias + residual in its epilogue.  The two sum in different orders, so a caller never changes its choice.
-template <typename T, typename SelfAttn>
+//   cross_attn(l)  optional: launches the layer's cross-attention from w.q into w.attn_t in place of cn_cross_attn_kernel
+//                  (conette_align: the kernel that also keeps the weights, dec_align.h)
+struct CnCrossDefault {};
+template <typename T, typename SelfAttn, typename CrossAttn = CnCrossDefault>
 static int dec_sublayer_layer(conette_ctx* ctx, const DecWs& w, int l, const int32_t* frame_lens, int R, int Ta, int rows_per_clip,
-                              bool ffn2_split, SelfAttn self_attn, hipStream_t s) {
+                              bool ffn2_split, SelfAttn self_attn, hipStream_t s, CrossAttn cross_attn = CrossAttn()) {
   const CnLayerW& lw = ctx->layers[l];
   const int d = ctx->cfg.d_model, dff = ctx->cfg.d_ff, kv_ld = ctx->cfg.n_layers * 2 * d;
   const float scale = 1.0f / sqrtf((float)(d / ctx->cfg.nhead));
@@ -964,8 +968,11 @@ static int dec_sublayer_layer(conette_ctx* ctx, const DecWs& w, int l, const int
   }
   {
     CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
-    hipLaunchKernelGGL((cn_cross_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, (T*)w.kvc, kv_ld, l * 2 * d, frame_lens, R,
-                       rows_per_clip, Ta, scale, attn_t);
+    if constexpr (std::is_same<CrossAttn, CnCrossDefault>::value)
+      hipLaunchKernelGGL((cn_cross_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, (T*)w.kvc, kv_ld, l * 2 * d, frame_lens, R,
+                         rows_per_clip, Ta, scale, attn_t);
+    else
+      cross_attn(l);
     CN_LAUNCH_CHECK();
   }
   {
@@ -1488,6 +1495,7 @@ extern "C" int32_t conette_decode_graph_nodes(const conette_ctx* ctx) {
 // conette_score runs the same pass over `cpa` captions per clip (rows r = (clip * cpa + caption) * cap_len + position; the
 // projection and the cross-attention K / V once per CLIP, the cross-attention's "beam" = cpa * cap_len) and ends in the fused
 // classifier + log-soft-max + gather of dec_score.h instead of the classifier GEMM.
+// conette_align is conette_score's pass with the cross-attention kernel of dec_align.h, which also stores the attention weights.
 template <typename T>
 __global__ __launch_bounds__(256) void cn_embed_caps_kernel(const int32_t* __restrict__ caps, const float* __restrict__ emb,
                                                             const float* __restrict__ pe, int cap_len, int R, float scale,
@@ -1549,10 +1557,10 @@ struct CnScoreOut {  // conette_score's tail of the pass
 template <typename T>
 static int forcing_prefill_impl(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* caps,
                                 int B, int Ta, int cpa, int cap_len, float* logits, const CnScoreOut* score, char* wsp,
-                                hipStream_t s) {
+                                hipStream_t s, const CnAlignOut* align = nullptr) {
   const conette_config& cfg = ctx->cfg;
   const int d = cfg.d_model, NL = cfg.n_layers, R = B * cpa * cap_len, V = cfg.vocab_size;
-  DecWs w = dec_ws(ctx, B, Ta, cpa * cap_len, 1, wsp, score != nullptr);  // rows = B * cpa * cap_len ("beam" = cpa * cap_len, one step)
+  DecWs w = dec_ws(ctx, B, Ta, cpa * cap_len, 1, wsp, score || align);  // rows = B * cpa * cap_len ("beam" = cpa * cap_len, one step)
   T* xt = (T*)w.xt;
   const float scale = 1.0f / sqrtf((float)(d / cfg.nhead));
   const int rblocks = cn_cdiv(R, 4);
@@ -1565,7 +1573,27 @@ static int forcing_prefill_impl(conette_ctx* ctx, const float* frame_embs, const
                        scale, (T*)w.attn_t);
   };
   // (ffn2_split = false at every precision: FFN2 as one GEMM is the summation order the outputs of this pass are defined by)
-  for (int l = 0; l < NL; ++l) CN_TRY((dec_sublayer_layer<T>(ctx, w, l, frame_lens, R, Ta, cpa * cap_len, false, self_attn, s)));
+  if (align) {  // conette_align: the cross-attention that keeps its weights (dec_align.h); the plain kernel where a layer has no output
+    const uint32_t sel = align->layer_mask;
+    const int first = __builtin_ctz(sel), last = 31 - __builtin_clz(sel);
+    const float inv_sel = 1.0f / (float)__builtin_popcount(sel);
+    const int kv_ld = NL * 2 * d;
+    auto cross_attn = [&](int l) {
+      const int mode = !((sel >> l) & 1) ? 0 : ((l == first ? AL_FIRST : AL_ADD) | (l == last ? AL_LAST : 0));
+      float* plane = align->attn_layers ? align->attn_layers + (size_t)l * R * Ta : nullptr;
+      if (mode == 0 && !plane)
+        hipLaunchKernelGGL((cn_cross_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, (T*)w.kvc, kv_ld, l * 2 * d, frame_lens, R,
+                           cpa * cap_len, Ta, scale, (T*)w.attn_t);
+      else
+        hipLaunchKernelGGL((cn_cross_attn_align_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.q, (T*)w.kvc, kv_ld, l * 2 * d,
+                           frame_lens, caps, cfg.pad_id, R, cpa * cap_len, Ta, scale, (T*)w.attn_t, plane, align->attn, mode, inv_sel);
+    };
+    for (int l = 0; l < NL; ++l)
+      CN_TRY((dec_sublayer_layer<T>(ctx, w, l, frame_lens, R, Ta, cpa * cap_len, false, self_attn, s, cross_attn)));
+    if (!score) return CN_OK;  // no targets: the classifier is not run
+  } else {
+    for (int l = 0; l < NL; ++l) CN_TRY((dec_sublayer_layer<T>(ctx, w, l, frame_lens, R, Ta, cpa * cap_len, false, self_attn, s)));
+  }
   CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
   if (score) {  // no logits: every row's log-probability of its target, summed per caption (dec_score.h)
     const int S = cn_score_slabs(R, V, ctx->n_cu, ctx->score_vsplit);
@@ -1649,6 +1677,53 @@ extern "C" int conette_score(conette_ctx* ctx, const float* frame_embs, const in
   const CnScoreOut out{targets, tok_lprobs, sum_lprobs, n_tokens};
   CN_BY_PRECISION(ctx, forcing_prefill_impl<OT>(ctx, frame_embs, frame_lens, caps_in, n_audio, t_audio, caps_per_audio, cap_len,
                                                 nullptr, &out, (char*)workspace, (hipStream_t)stream));
+}
+
+// ---- alignment (dec_align.h): conette_score's pass with the cross-attention weights kept ----
+extern "C" size_t conette_align_workspace_bytes(const conette_ctx* ctx, int32_t n_audio, int32_t t_audio, int32_t caps_per_audio,
+                                                int32_t cap_len, int32_t with_scores) {
+  if (!ctx || n_audio <= 0 || t_audio <= 0 || caps_per_audio <= 0 || cap_len <= 0) return 0;
+  const long rows = (long)n_audio * caps_per_audio * cap_len;
+  if (rows > 0x7fffffffL / 4096) return 0;  // (as conette_score)
+  const int R = (int)rows;
+  const size_t lean = dec_ws(ctx, n_audio, t_audio, caps_per_audio * cap_len, 1, nullptr, true).total;
+  if (!with_scores) return lean;
+  return lean + cn_score_part_bytes(R, cn_score_slabs(R, ctx->cfg.vocab_size, ctx->n_cu, ctx->score_vsplit));
+}
+
+extern "C" int conette_align(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* caps_in,
+                             const int32_t* targets, int32_t n_audio, int32_t t_audio, int32_t caps_per_audio, int32_t cap_len,
+                             uint32_t layer_mask, float* attn, float* attn_layers, float* tok_lprobs, float* sum_lprobs,
+                             int32_t* n_tokens, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ctx || !frame_embs || !frame_lens || !caps_in || !attn || !workspace || n_audio <= 0 || t_audio <= 0) {
+    cn_set_error("align: bad argument");
+    return CN_ERR_ARG;
+  }
+  if (targets ? (!sum_lprobs || !n_tokens) : (tok_lprobs || sum_lprobs || n_tokens)) {
+    cn_set_error("align: sum_lprobs and n_tokens go with targets (all given, or all NULL together with tok_lprobs)");
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_model(ctx, "align", cap_len, 0, "align: cap_len=%d unsupported (1..%d)", cap_len, CN_MAX_PRED));
+  if (caps_per_audio < 1) {
+    cn_set_error("align: caps_per_audio=%d < 1", caps_per_audio);
+    return CN_ERR_ARG;
+  }
+  const int NL = ctx->cfg.n_layers;
+  const uint32_t all = NL >= 32 ? ~0u : ((1u << NL) - 1u);
+  if (layer_mask & ~all) {
+    cn_set_error("align: layer_mask=0x%x selects a layer at or above n_layers=%d", layer_mask, NL);
+    return CN_ERR_ARG;
+  }
+  const size_t need = conette_align_workspace_bytes(ctx, n_audio, t_audio, caps_per_audio, cap_len, targets != nullptr);
+  if (need == 0) {
+    cn_set_error("align: %d x %d x %d rows in one call are too many (split the call)", n_audio, caps_per_audio, cap_len);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_workspace("align", workspace_bytes, need));
+  const CnScoreOut out{targets, tok_lprobs, sum_lprobs, n_tokens};
+  const CnAlignOut al{attn, attn_layers, layer_mask ? layer_mask : all};
+  CN_BY_PRECISION(ctx, forcing_prefill_impl<OT>(ctx, frame_embs, frame_lens, caps_in, n_audio, t_audio, caps_per_audio, cap_len,
+                                                nullptr, targets ? &out : nullptr, (char*)workspace, (hipStream_t)stream, &al));
 }
 
 extern "C" int conette_greedy(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,

@@ -33,6 +33,7 @@ EXPORTS = (
     "conette_stream_destroy", "conette_forcing_workspace_bytes", "conette_forcing",
     "conette_greedy_workspace_bytes", "conette_greedy", "conette_decode_graph_nodes", "conette_encode_nonfinite",
     "conette_score_workspace_bytes", "conette_score", "conette_sample_workspace_bytes", "conette_sample",
+    "conette_align_workspace_bytes", "conette_align",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -141,6 +142,12 @@ def load_library() -> C.CDLL:
     lib.conette_score.restype = C.c_int
     lib.conette_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_align_workspace_bytes.restype = C.c_size_t
+    lib.conette_align_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_align.restype = C.c_int
+    lib.conette_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]
     lib.conette_sample_workspace_bytes.restype = C.c_size_t
     lib.conette_sample_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.conette_sample.restype = C.c_int
@@ -626,6 +633,60 @@ class Engine:
                                         _ptr(wsb), wsb.numel(), _stream())
             _check(st, "conette_score")
         return {"tok_lprobs": tok, "sum_lprobs": sums, "n_tokens": cnt}
+
+    def align(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, caps_in: torch.Tensor,
+              targets: Optional[torch.Tensor] = None, caps_per_audio: int = 1, layers=None,
+              per_layer: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+        """Where in the clip each caption position listens (conette_align, include/conette_hip.h): the head-mean cross-attention of
+        the one-pass decoder, averaged over ``layers`` (decoder layer indices; None = all).  Inputs as in ``score``; ``targets``
+        is optional -- without it the classifier does not run and the three score entries are None.  Returns {"attn": (P, cap_len,
+        T) fp32 -- row t belongs to the position that predicts targets[:, t]; exactly 0 behind the clip's length and in rows of
+        pad inputs --, "attn_layers": (n_layers, P, cap_len, T) when ``per_layer`` else None, "tok_lprobs", "sum_lprobs",
+        "n_tokens": ``score``'s, bit for bit}.  The id check and the chunking by ``score_workspace_bound`` are ``score``'s."""
+        from . import scoring
+        n, t, _ = frame_embs.shape
+        cpa, cap_len = int(caps_per_audio), int(caps_in.shape[1])
+        if cpa < 1 or caps_in.ndim != 2 or caps_in.shape[0] != n * cpa or (targets is not None and tuple(caps_in.shape) != tuple(targets.shape)):
+            raise ValueError(f"align: caps_in {tuple(caps_in.shape)}" + ("" if targets is None else f" / targets {tuple(targets.shape)}") +
+                             f" do not hold {n} x {cpa} captions of one length")
+        mask = 0
+        for l in (() if layers is None else layers):
+            if not 0 <= int(l) < self.n_layers:
+                raise ValueError(f"align: layer {l} outside [0, {self.n_layers})")
+            mask |= 1 << int(l)
+        if layers is not None and mask == 0:
+            raise ValueError("align: no layer selected")
+        if not torch.cuda.is_current_stream_capturing() and caps_in.numel() > 0:
+            lo, hi = int(caps_in.min()), int(caps_in.max())
+            if lo < 0 or hi >= self.vocab_size:
+                raise ValueError(f"align: caps_in ids must lie in [0, {self.vocab_size}), found [{lo}, {hi}]")
+        fe = frame_embs.to(self.device, torch.float32).contiguous()
+        lens = frame_lens.to(self.device, torch.int32).contiguous()
+        caps = caps_in.to(self.device, torch.int32).contiguous()
+        tgt = None if targets is None else targets.to(self.device, torch.int32).contiguous()
+        p = n * cpa
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        attn = e((p, cap_len, t), torch.float32)
+        planes = e((self.n_layers, p, cap_len, t), torch.float32) if per_layer else None
+        tok = e((p, cap_len), torch.float32) if tgt is not None else None
+        sums = e((p,), torch.float32) if tgt is not None else None
+        cnt = e((p,), torch.int32) if tgt is not None else None
+        ctx = self._ctx_dec
+        need = lambda nc, mc: int(self.lib.conette_align_workspace_bytes(ctx, nc, t, mc, cap_len, int(tgt is not None))) or (1 << 62)
+        bound = int(getattr(self, "score_workspace_bound", scoring.SCORE_WORKSPACE_BOUND))
+        sl = lambda x, rows: None if x is None else x[rows]
+        for i0, nc, j0, mc in scoring.plan_chunks(n, cpa, need, bound):
+            rows = slice(i0 * cpa, (i0 + nc) * cpa) if mc == cpa else slice(i0 * cpa + j0, i0 * cpa + j0 + mc)
+            whole = rows.stop - rows.start == p
+            part = planes if (planes is None or whole) else e((self.n_layers, rows.stop - rows.start, cap_len, t), torch.float32)
+            wsb = self._workspace("score", need(nc, mc))
+            st = self.lib.conette_align(ctx, _ptr(fe[i0:i0 + nc]), _ptr(lens[i0:i0 + nc]), _ptr(caps[rows]), _ptr(sl(tgt, rows)), nc, t,
+                                        mc, cap_len, mask, _ptr(attn[rows]), _ptr(part), _ptr(sl(tok, rows)), _ptr(sl(sums, rows)),
+                                        _ptr(sl(cnt, rows)), _ptr(wsb), wsb.numel(), _stream())
+            _check(st, "conette_align")
+            if part is not planes:   # (a chunk's planes are (n_layers, its rows, ...): copied into place)
+                planes[:, rows].copy_(part)
+        return {"attn": attn, "attn_layers": planes, "tok_lprobs": tok, "sum_lprobs": sums, "n_tokens": cnt}
 
     def set_score_vsplit(self, slabs: int) -> None:
         """Vocabulary slabs of conette_score's fused kernel: 0 = chosen from the row count (default), k >= 1 = k (clamped)."""

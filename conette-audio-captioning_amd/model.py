@@ -294,6 +294,21 @@ class CoNeTTEModel:
                 source_lst[i] = "_".join(parts[1:])
         return tasks, dataset_lst, source_lst
 
+    def _encoder_overflowed(self, preprocess: bool) -> bool:
+        """Did the encode that just ran overflow?  Raises unless the precision can re-run the batch exactly."""
+        if not (preprocess and self.engine.precision in (PREC_BF16, PREC_F16)):
+            return False
+        # the fp16 residual stream of the 16-bit encoders holds |x| <= 65504; beyond it the embeddings are garbage
+        # (include/conette_hip.h: conette_encode_nonfinite).  The certified precision re-runs the whole batch through
+        # the exact context (fp32 stream) then; the others fail loudly.
+        bad = self.engine.encode_nonfinite()
+        if bad and not self.engine.certified:
+            raise RuntimeError(
+                f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
+                "positions with non-finite LayerNorm statistics); use precision='certified', 'exact' or 'fp32' for "
+                "this checkpoint")
+        return bad > 0
+
     # ---- forward (model.py:185-261) -----------------------------------------------------------------
     @torch.no_grad()
     def forward(self, x: Union[Tensor, str, Iterable[str], Iterable[Tensor]],
@@ -316,18 +331,7 @@ class CoNeTTEModel:
             bsize = len(batch["audio"])
             tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
 
-            overflow = False
-            if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
-                # the fp16 residual stream of the 16-bit encoders holds |x| <= 65504; beyond it the embeddings are garbage
-                # (include/conette_hip.h: conette_encode_nonfinite).  The certified precision re-runs the whole batch through
-                # the exact context (fp32 stream) then; the others fail loudly.
-                bad = self.engine.encode_nonfinite()
-                if bad and not self.engine.certified:
-                    raise RuntimeError(
-                        f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
-                        "positions with non-finite LayerNorm statistics); use precision='certified', 'exact' or 'fp32' for "
-                        "this checkpoint")
-                overflow = bad > 0
+            overflow = self._encoder_overflowed(preprocess)
             outs = self._generate(batch["audio"], batch["audio_shape"], dataset_lst, source_lst,
                                   beam_size=beam_size, min_pred_size=min_pred_size, max_pred_size=max_pred_size,
                                   forbid_rep_mode=forbid_rep_mode, wave=wave, recompute_all=overflow)
@@ -436,6 +440,53 @@ class CoNeTTEModel:
         logits = self.engine.forcing(audio, lens, caps_in)  # (B, cap_len, V)
         return logits.permute(0, 2, 1)
 
+    # ---- what score_captions and align_captions share: the clips' frame embeddings and the captions as rows of the engine ----
+    @staticmethod
+    def _check_captions(captions, pairwise: bool = False) -> Tensor:
+        captions = torch.as_tensor(captions)
+        if captions.is_floating_point() or captions.ndim not in ((2,) if pairwise else (2, 3)):
+            raise ValueError("captions must be an integer tensor of shape (bsize, caps_size) or (bsize, n_caps, caps_size)"
+                             " -- (n_caps, caps_size) with pairwise=True.")
+        return captions
+
+    def _frame_embeddings(self, x, sr, x_shapes, preprocess: bool, keep: Optional[dict] = None):
+        """(audio (B, T, 768), audio_shape (B, 2)) of ``x`` as ``teacher_forcing`` takes it; ``keep`` receives the preprocessor's
+        other outputs."""
+        if preprocess:
+            batch = self.preprocessor(x, sr, x_shapes)
+            audio, audio_shape = batch["audio"], batch["audio_shape"]
+            if keep is not None:
+                keep.update({k: v for k, v in batch.items() if k not in ("audio", "audio_shape")})
+        elif isinstance(x, dict):
+            audio, audio_shape = x["audio"], x["audio_shape"]
+        else:
+            audio = x
+            audio_shape = x_shapes if x_shapes is not None else torch.as_tensor([list(a.shape) for a in x])
+        if audio.ndim == 4:
+            audio = audio.squeeze(dim=1)
+        return audio, audio_shape
+
+    def _caption_rows(self, captions: Tensor, bsize: int, task, pairwise: bool = False):
+        """(caps_in, targets (bsize * n_caps, size - 1) int32, n_caps, size) of full captions, <bos> replaced by the task token"""
+        from . import scoring
+        caps3 = scoring.pairwise_captions(captions, bsize) if pairwise else (captions[:, None] if captions.ndim == 2 else captions)
+        if caps3.shape[0] != bsize:
+            raise ValueError(f"Invalid number of captions {caps3.shape[0]} for {bsize} audio clips.")
+        task_ids = None
+        if task is not None:
+            tasks = [task] * bsize if isinstance(task, str) else list(task)
+            if len(tasks) != bsize:
+                raise ValueError(f"Invalid number of tasks with input. (found {len(tasks)} tasks but {bsize} elements)")
+            for name in tasks:
+                if name not in self.config.task_names:
+                    raise ValueError(f"Invalid argument {tasks=}. (task {name} is not in {self.config.task_names})")
+            parts = [name.split("_") for name in tasks]
+            task_ids = self.batch_to_task_token_ids([q[0] for q in parts], ["_".join(q[1:]) if len(q) >= 2 else None for q in parts])
+        caps3 = scoring.replace_bos(caps3.cpu(), self.tokenizer.bos_token_id, task_ids)
+        n_caps, size = int(caps3.shape[1]), int(caps3.shape[2])
+        caps_in, targets = scoring.split_captions(caps3.reshape(bsize * n_caps, size), self.tokenizer.pad_token_id)
+        return caps_in, targets, n_caps, size
+
     def score_captions(self, x, captions: Tensor, sr=None, x_shapes=None, preprocess: bool = True,
                        task: Union[str, List[str], None] = None, pairwise: bool = False) -> Dict[str, Tensor]:
         """How likely given captions are for given clips -- the quantity CoNeTTEPLM.validation_step / test_step report
@@ -450,44 +501,73 @@ class CoNeTTEModel:
         "losses": (B, n_caps) the reference's ``losses``, "loss": their mean}.  Precision "certified" scores through its
         16-bit base context, like ``teacher_forcing``."""
         from . import scoring
-        captions = torch.as_tensor(captions)
-        if captions.is_floating_point() or captions.ndim not in ((2,) if pairwise else (2, 3)):
-            raise ValueError("captions must be an integer tensor of shape (bsize, caps_size) or (bsize, n_caps, caps_size)"
-                             " -- (n_caps, caps_size) with pairwise=True.")
+        captions = self._check_captions(captions, pairwise)
         with torch.cuda.device(self.device):
-            if preprocess:
-                batch = self.preprocessor(x, sr, x_shapes)
-                audio, audio_shape = batch["audio"], batch["audio_shape"]
-            elif isinstance(x, dict):
-                audio, audio_shape = x["audio"], x["audio_shape"]
-            else:
-                audio = x
-                audio_shape = x_shapes if x_shapes is not None else torch.as_tensor([list(a.shape) for a in x])
-            if audio.ndim == 4:
-                audio = audio.squeeze(dim=1)
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess)
             bsize = int(audio.shape[0])
-            caps3 = scoring.pairwise_captions(captions, bsize) if pairwise else (captions[:, None] if captions.ndim == 2 else captions)
-            if caps3.shape[0] != bsize:
-                raise ValueError(f"Invalid number of captions {caps3.shape[0]} for {bsize} audio clips.")
-            task_ids = None
-            if task is not None:
-                tasks = [task] * bsize if isinstance(task, str) else list(task)
-                if len(tasks) != bsize:
-                    raise ValueError(f"Invalid number of tasks with input. (found {len(tasks)} tasks but {bsize} elements)")
-                for name in tasks:
-                    if name not in self.config.task_names:
-                        raise ValueError(f"Invalid argument {tasks=}. (task {name} is not in {self.config.task_names})")
-                parts = [name.split("_") for name in tasks]
-                task_ids = self.batch_to_task_token_ids([q[0] for q in parts], ["_".join(q[1:]) if len(q) >= 2 else None for q in parts])
-            caps3 = scoring.replace_bos(caps3.cpu(), self.tokenizer.bos_token_id, task_ids)
-            n_caps, size = int(caps3.shape[1]), int(caps3.shape[2])
-            caps_in, targets = scoring.split_captions(caps3.reshape(bsize * n_caps, size), self.tokenizer.pad_token_id)
+            caps_in, targets, n_caps, size = self._caption_rows(captions, bsize, task, pairwise)
             lens = torch.as_tensor(audio_shape)[:, 1].to(torch.int32)
             res = self.engine.score(audio, lens, caps_in, targets, caps_per_audio=n_caps)
             sums, cnt = res["sum_lprobs"].reshape(bsize, n_caps), res["n_tokens"].reshape(bsize, n_caps)
             losses = scoring.losses_from(sums, cnt)
             return {"lprobs": res["tok_lprobs"].reshape(bsize, n_caps, size - 1), "sum_lprobs": sums, "n_tokens": cnt,
                     "losses": losses, "loss": losses.mean()}
+
+    @torch.no_grad()
+    def align_captions(self, x, captions: Optional[Tensor] = None, sr=None, x_shapes=None, preprocess: bool = True,
+                       task: Union[str, List[str], None] = None, layers=None, per_layer: bool = False, mass: float = 0.5,
+                       **search_kwargs) -> Dict[str, Any]:
+        """WHERE in the clip each word of a caption is heard: the decoder's cross-attention over the encoder's 0.32 s frames,
+        mean over heads and over ``layers`` (decoder layer indices; None = all), from the one causal pass that scores the
+        caption (conette_align; alignment.py reads the maps).
+
+        ``x``, ``captions`` ((B, L) or (B, n_caps, L) FULL captions) and ``task`` as in ``score_captions``.  With
+        ``captions=None`` the clips are captioned first -- ``forward``'s search on the same encoder output, ``search_kwargs`` =
+        its beam_size / min_pred_size / max_pred_size / forbid_rep_mode -- and each clip's best caption is aligned (task token +
+        prediction through <eos>; n_caps = 1); "cands" / "preds" are returned too.
+        Returns {"attn": (B, n_caps, L - 1, T) -- row t is the position that PREDICTS token t + 1, so it is labelled with it:
+        "tokens" (B, n_caps, L - 1) (= the targets), "lprobs": ``score_captions``'s, "peak_time" /
+        "mean_time" (B, n_caps, L - 1) and "span_time" (B, n_caps, L - 1, 2) in seconds from the clip's start (the centre of the
+        strongest frame, the centre of mass, the shortest window holding ``mass`` of the weight; NaN where the token is pad_id),
+        "frame_sec",
+        "sum_lprobs", "n_tokens" [, "attn_layers": (n_layers, B, n_caps, L - 1, T) with ``per_layer``]}.  Precision "certified"
+        aligns through its 16-bit base context, like ``score_captions``."""
+        from . import alignment
+        if captions is not None:
+            if search_kwargs:
+                raise TypeError(f"align_captions: {sorted(search_kwargs)} belong to the search, which given captions do not run")
+            captions = self._check_captions(captions)
+        with torch.cuda.device(self.device):
+            extra: Dict[str, Any] = {}
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess, keep=extra)
+            audio_shape = torch.as_tensor(audio_shape)
+            bsize = int(audio.shape[0])
+            outs: Dict[str, Any] = {}
+            if captions is None:
+                tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
+                gen = self._generate(audio, audio_shape.to(audio.device), dataset_lst, source_lst, wave=extra.get("_wave"),
+                                     recompute_all=self._encoder_overflowed(preprocess), **search_kwargs)
+                gen.pop("_clip_probs_patch", None)
+                outs.update(cands=gen["cands"], preds=gen["preds"], tasks=tasks)
+                preds = gen["preds"].cpu()
+                ended = (preds == self.tokenizer.eos_token_id).long().cumsum(dim=1) - (preds == self.tokenizer.eos_token_id).long()
+                preds = torch.where(ended > 0, torch.full_like(preds, self.tokenizer.pad_token_id), preds)   # nothing after <eos>
+                first = self.batch_to_task_token_ids(dataset_lst, source_lst).cpu().to(preds.dtype)
+                captions, task = torch.cat([first[:, None], preds], dim=1), None
+            caps_in, targets, n_caps, size = self._caption_rows(captions, bsize, task)
+            lens = audio_shape[:, 1].to(torch.int32)
+            res = self.engine.align(audio, lens, caps_in, targets, caps_per_audio=n_caps, layers=layers, per_layer=per_layer)
+            t = int(audio.shape[1])
+            attn = res["attn"].reshape(bsize, n_caps, size - 1, t)
+            tokens = targets.reshape(bsize, n_caps, size - 1).to(attn.device)
+            labelled = attn * tokens.ne(self.tokenizer.pad_token_id)[..., None]   # (a row that predicts a pad has no word to place)
+            outs.update(attn=attn, tokens=tokens,
+                        lprobs=res["tok_lprobs"].reshape(bsize, n_caps, size - 1),
+                        sum_lprobs=res["sum_lprobs"].reshape(bsize, n_caps), n_tokens=res["n_tokens"].reshape(bsize, n_caps),
+                        frame_sec=alignment.FRAME_SEC, **alignment.times(labelled, lens.to(attn.device), mass))
+            if per_layer:
+                outs["attn_layers"] = res["attn_layers"].reshape(-1, bsize, n_caps, size - 1, t)
+            return outs
 
     def greedy_search(self, x, sr=None, x_shapes=None, preprocess: bool = True, bos_id: Optional[int] = None,
                       min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,

@@ -3,7 +3,7 @@
 
     python -m conette_amd.predict --audio a.wav b.wav --task clotho --model_name DIR_OR_HUB_NAME \
         [--csv_export out.csv] [--precision certified|certified:BASE|bf16|bf16+f16dec|f16|mixed|mixed16|exact|fp32]
-        [--sample N --temperature T --top_k K --top_p P --seed S]
+        [--sample N --temperature T --top_k K --top_p P --seed S] [--align]
 
 ``--model_path`` (a Lightning training log directory with hydra/config.yaml + checkpoints/best.ckpt, predict.py:123-178) is
 accepted when the audio encoder's weights come with it: the reference builds its HF wrapper around the Lightning module and leaves
@@ -53,6 +53,11 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
     parser.add_argument("--temperature", type=float, help="With --sample: softmax temperature.", default=1.0)
     parser.add_argument("--top_k", type=int, help="With --sample: keep the k most likely tokens (0: off).", default=0)
     parser.add_argument("--top_p", type=float, help="With --sample: nucleus mass (1: off).", default=1.0)
+    parser.add_argument("--align", action="store_true",
+                        help="One row per word of each file's caption -- audio, task, word, start, end (seconds) -- instead of one per file: "
+                             "where in the clip the decoder listens while it predicts the word (CoNeTTEModel.align_captions).")
+    parser.add_argument("--align_mass", type=float, default=0.5,
+                        help="With --align: start .. end is the shortest window holding this share of the word's attention.")
     parser.add_argument("--csv_export", type=_opt_str, help="Path to CSV output file.", default=None)
     parser.add_argument("--verbose", type=int, help="Verbose level.", default=1)
     parser.add_argument("--precision", type=str, default=None,
@@ -66,9 +71,18 @@ def format_results(fpaths: List[str], tasks: List[str], cands: List[str]) -> Lis
     return [{"audio": osp.basename(f), "task": t, "candidate": c} for f, t, c in zip(fpaths, tasks, cands)]
 
 
+def format_alignment(fpaths: List[str], tasks: List[str], tokenizer, outs: dict) -> List[dict]:
+    """Rows of ``--align``: the words of each file's aligned caption (n_caps = 1) in order, special tokens left out, with the
+    span of ``align_captions`` in seconds."""
+    special = (tokenizer.pad_token_id, tokenizer.bos_token_id, tokenizer.eos_token_id)
+    tokens, spans = outs["tokens"][:, 0].tolist(), outs["span_time"][:, 0].tolist()
+    return [{"audio": osp.basename(f), "task": t, "word": tokenizer.id_to_token(tok), "start": f"{lo:.2f}", "end": f"{hi:.2f}"}
+            for f, t, row, sp in zip(fpaths, tasks, tokens, spans) for tok, (lo, hi) in zip(row, sp) if tok not in special]
+
+
 def write_csv(path: str, results: List[dict]) -> None:
     with open(path, "w") as file:
-        writer = csv.DictWriter(file, fieldnames=["audio", "task", "candidate"])
+        writer = csv.DictWriter(file, fieldnames=list(results[0]) if results else ["audio", "task", "candidate"])
         writer.writeheader()
         writer.writerows(results)
 
@@ -154,6 +168,17 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
     tasks = args.task
     if tasks is not None and len(tasks) == 1:
         tasks = tasks[0]
+    if args.align and args.sample > 0:
+        raise ValueError("--align places the words of the searched caption; it does not go with --sample")
+    if args.align:        # one row per word of the best caption
+        outs = model.align_captions(fpaths, task=tasks, mass=args.align_mass)
+        results = format_alignment(fpaths, outs["tasks"], model.tokenizer, outs)
+        for f, t, c in zip(fpaths, outs["tasks"], outs["cands"]):
+            words = " ".join(f"{r['word']}[{r['start']}-{r['end']}]" for r in results if r["audio"] == osp.basename(f))
+            pylog.info(f"File '{osp.basename(f)}' with task '{t}':\n - '{c}'\n - {words}")
+        if args.csv_export is not None:
+            write_csv(args.csv_export, results)
+        return results
     if args.sample > 0:   # N draws per file, in the order drawn
         outs = model.sample(fpaths, num_samples=args.sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                             seed=args.seed, task=tasks)

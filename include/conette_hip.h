@@ -194,6 +194,29 @@ int conette_score(conette_ctx* ctx, const float* frame_embs, const int32_t* fram
                   float* tok_lprobs, float* sum_lprobs, int32_t* n_tokens, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* Word-to-audio alignment of given captions: conette_score's one causal pass with the decoder's cross-attention weights kept --
+ * for every caption position a distribution over the clip's encoder frames (one frame = 32 STFT hops = 0.32 s at 32 kHz).
+ * Row (p, t) belongs to the query at position t of caption p, the one that PREDICTS targets[p][t]; per layer the weights are the
+ * mean over the 8 heads of softmax_frames(q_h . k_h / sqrt(32)), computed from the same scores, maxima and sums as the context
+ * vector the layer goes on with (p_h = exp(s_h - m_h) * (1 / l_h), heads added in ascending order, times 1 / 8).
+ *   caps_in, targets, P, cap_len, caps_per_audio : conette_score's contract; targets may be NULL: then the classifier is not run,
+ *                and tok_lprobs, sum_lprobs and n_tokens must be NULL too (with targets, sum_lprobs and n_tokens are required and
+ *                hold exactly conette_score's results)
+ *   layer_mask  : bit l = decoder layer l takes part in `attn`; 0 = all layers; a bit at or above n_layers is an error
+ *   attn        : dev (P, cap_len, t_audio) fp32, the mean over the selected layers in ascending order (sum, then times
+ *                 1 / n_selected); no memset needed
+ *   attn_layers : dev (n_layers, P, cap_len, t_audio) fp32 or NULL -- every layer's own weights, selected or not
+ * Frames at or behind frame_lens[clip] are exactly 0, and so is every frame of a row whose caps_in token is pad_id, whatever the
+ * buffers held; every other row sums to 1 up to rounding.  cap_len <= 64, caps_per_audio >= 1, t_audio unbounded.  Asynchronous on
+ * `stream`, capturable; results are bit-identical from run to run.  Works on decoder-only contexts and in every precision.  The
+ * workspace is conette_score's without the score partials unless `with_scores`; nothing of size rows x frames x heads exists. */
+size_t conette_align_workspace_bytes(const conette_ctx* ctx, int32_t n_audio, int32_t t_audio, int32_t caps_per_audio,
+                                     int32_t cap_len, int32_t with_scores);
+int conette_align(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* caps_in,
+                  const int32_t* targets, int32_t n_audio, int32_t t_audio, int32_t caps_per_audio, int32_t cap_len,
+                  uint32_t layer_mask, float* attn, float* attn_layers, float* tok_lprobs, float* sum_lprobs, int32_t* n_tokens,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* greedy_search (nn/decoding/greedy.py:17-131; BaselinePLM's decoder, not reachable from
  * CoNeTTEPLM): the arg-max chain with the full masked logits of every step as output.
  *   logits : dev (B, max_pred, vocab) fp32 -- per step the logits of every unfinished clip with the EOS floor
