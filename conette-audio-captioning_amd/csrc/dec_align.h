@@ -1,6 +1,6 @@
 // Word-to-audio alignment: the cross-attention of the one-pass teacher forcing with its weights kept (conette_align, decoder.hip).
 //
-// cn_cross_attn_align_kernel<T> is cn_cross_attn_kernel<T> for a row -- same row / lane layout, same online soft-max, the same
+// cn_cross_attn_align_kernel<T> is cn_cross_attn_kernel<T> (dec_rows.h) for a row -- same row / lane layout, same online soft-max, the same
 // context vector bit for bit -- and additionally writes the row's attention weights, averaged over the 8 heads:
 //   pass 1  the online soft-max over the clip's frames; each batch's 8 x 8 scores are parked in LDS, [head][frame] per wave
 //           (the first lane of each head stores its 8 scores as two 16-byte writes; the head stride of AL_LD = AL_TILE + 8 floats

@@ -2,7 +2,7 @@
 // GEMM leaves in the workspace (conette_sample, include/conette_hip.h; the CPU restatement of the rule is conette_amd/sampling.py).
 //
 // Rows = clips x samples.  A row never changes its parent, so the step is row-local: one block of 1024 threads per row.
-//   masks      EOS floor while step < min_pred, forbid-repeat over the row's prefix -- as the searches apply them
+//   masks      EOS floor while step < min_pred, forbid-repeat over the row's prefix -- the searches' rule (dec_search.h)
 //   log-prob   log_softmax(masked z)[token] at temperature 1, unfiltered: (z_t - max) - log(sum exp(z - max))
 //   top-k      v kept iff fewer than k tokens have a strictly larger logit      = key(v) >= the k-th largest key
 //   top-p      v kept iff the mass of the strictly larger logits is < p         = key(v) >= the largest t with mass(key >= t) >= p * S
@@ -17,6 +17,8 @@
 // holds reduction scratch only.  Generic variant (VPT = 0, V <= 65536): the same code re-reading (and re-masking) the logits from
 // global memory in every phase.
 #pragma once
+
+#include "dec_search.h"
 
 #define SM_T 1024
 #define SM_VPT 8          // most logits per thread of the register variant: V <= 8192
@@ -161,19 +163,7 @@ __global__ __launch_bounds__(SM_T) void cn_sample_step_kernel(const SmArgs a, co
   }
   __syncthreads();
   if constexpr (REG) {  // forbid-repeat over the prefix (position 0 included) and the EOS floor, on the owner's registers
-    for (int j = 0; j <= step; ++j) {
-      const int tok = s_prefix[j];
-      if ((tok & (SM_T - 1)) == tid) {
-#pragma unroll
-        for (int sl = 0; sl < VPT; ++sl)
-          if (sl == (tok >> 10) && fb[sl]) val[sl] = -INFINITY;
-      }
-    }
-    if (step < a.min_pred && (eos & (SM_T - 1)) == tid) {
-#pragma unroll
-      for (int sl = 0; sl < VPT; ++sl)
-        if (sl == (eos >> 10)) val[sl] = -INFINITY;
-    }
+    cn_mask_registers<SM_T>(val, fb, s_prefix, step, a.min_pred, eos, tid, wv);
 #pragma unroll
     for (int sl = 0; sl < VPT; ++sl) val[sl] += 0.f;  // -0 -> +0: equal floats, equal keys
   }
@@ -184,14 +174,7 @@ __global__ __launch_bounds__(SM_T) void cn_sample_step_kernel(const SmArgs a, co
     } else {
       const int v = sl * SM_T + tid;
       if (v >= V) return -INFINITY;
-      float x = lg[v];
-      if (step < a.min_pred && v == eos) x = -INFINITY;
-      if (a.forbid != nullptr && a.forbid[v] != 0) {
-        bool seen = false;
-        for (int j = 0; j <= step; ++j) seen |= s_prefix[j] == v;
-        if (seen) x = -INFINITY;
-      }
-      return x + 0.f;
+      return cn_masked_logit(lg, v, step, a.min_pred, eos, a.forbid, s_prefix) + 0.f;
     }
   };
 #define SM_FOR(sl) _Pragma("unroll") for (int sl = 0; sl < (REG ? VPT : nsl); ++sl)

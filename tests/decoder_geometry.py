@@ -9,6 +9,8 @@ Sources mirrored (paths under conette-audio-captioning_amd/csrc):
   * decoder.hip ``decode_impl``: the search step (``cn_search_step3_kernel<NR, VPT>`` for V <= S3_T * S3_VPT and beam <= 8, the
     generic ``cn_search_step_kernel`` otherwise), the FFN path of a step (fused ``cn_dec_ffn_kernel`` with d_ff / 256 slabs, the
     block kernel + two ``cn_gemm2`` launches, or one launch per sub-layer), the split-K of FFN2 and the rows per block.
+  * dec_search.h: the two search-step kernels and their limits (``S3_T``, ``S3_VPT``, ``CN_MAX_BEAM``, ``CN_MAX_PRED``);
+    dec_rows.h: keys per batch of the unfused attention kernels.
   * api.hip ``conette_create``: which geometries get the packed FFN stream (``d_ff % 256 == 0 && d_ff <= 2048``).
   * gemm2.h ``cn_gemm2``: BK = 32 tiles when K is no multiple of 64.
   * dec_block.h / dec_ffn.h / ctx.h: rows per block, keys per batch and batches in flight, rows per FFN tile, layer limit.
@@ -18,12 +20,12 @@ from __future__ import annotations
 
 from typing import Dict, List, NamedTuple, Optional, Set, Tuple
 
-S3_T = 1024                      # decoder.hip: #define S3_T 1024 (threads of the register-resident search step)
-S3_VPT = 8                       # decoder.hip: #define S3_VPT 8 (most logits per thread: V <= 8192)
+S3_T = 1024                      # dec_search.h: #define S3_T 1024 (threads of the register-resident search step)
+S3_VPT = 8                       # dec_search.h: #define S3_VPT 8 (most logits per thread: V <= 8192)
 S3_MAX_BEAM = 8                  # decoder.hip: if (V <= S3_T * S3_VPT && beam <= 8)
 S3_KERNELS = ((4, 2), (4, 4), (4, 6), (4, 8), (8, 4), (8, 8))   # decoder.hip: the S3_LAUNCH(NR, VPT) instantiations
-CN_MAX_BEAM = 16                 # decoder.hip: #define CN_MAX_BEAM 16
-CN_MAX_PRED = 64                 # decoder.hip: #define CN_MAX_PRED 64
+CN_MAX_BEAM = 16                 # dec_search.h: #define CN_MAX_BEAM 16
+CN_MAX_PRED = 64                 # dec_search.h: #define CN_MAX_PRED 64
 FF2_SPLITS = 8                   # decoder.hip: #define FF2_SPLITS 8 (most slabs; split-K of the per-sub-layer FFN2)
 FF2_SPLITS_DEFAULT = 4           # decoder.hip: ff2_splits_default() (split-K of FFN2 behind the block kernel)
 FUSED_FFN_MAX = 2048             # api.hip: dff % 256 == 0 && dff <= 2048 (the packed stream of cn_dec_ffn_kernel)
@@ -38,7 +40,7 @@ DB_NB_SELF = 8                   # dec_block.h: self-attention keys per batch
 DB_DEPTH_SELF = 2                # dec_block.h: batches in flight
 DB_NB_CROSS = 8                  # dec_block.h: cross-attention frames per batch
 DB_DEPTH_CROSS = 2
-ATTN_NB = 8                      # decoder.hip: constexpr int NB = 8 (keys per batch of the unfused attention kernels)
+ATTN_NB = 8                      # dec_rows.h: constexpr int NB = 8 (keys per batch of the unfused attention kernels)
 CN_MAX_LAYERS = 12               # ctx.h: #define CN_MAX_LAYERS 12
 D_MODEL = 256
 N_SPECIALS_AND_TASKS = 11        # synth: 4 special tokens + 7 task tokens; V = n_words + 11

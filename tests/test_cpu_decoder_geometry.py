@@ -30,11 +30,11 @@ def _one(pattern, text):
 
 
 def test_search_dispatch_matches_the_sources():
-    dec = _src("decoder.hip")
-    assert _one(r"#define S3_T (\d+)", dec) == D.S3_T
-    assert _one(r"#define S3_VPT (\d+)", dec) == D.S3_VPT
-    assert _one(r"#define CN_MAX_BEAM (\d+)", dec) == D.CN_MAX_BEAM
-    assert _one(r"#define CN_MAX_PRED (\d+)", dec) == D.CN_MAX_PRED
+    dec, srch = _src("decoder.hip"), _src("dec_search.h")
+    assert _one(r"#define S3_T (\d+)", srch) == D.S3_T
+    assert _one(r"#define S3_VPT (\d+)", srch) == D.S3_VPT
+    assert _one(r"#define CN_MAX_BEAM (\d+)", srch) == D.CN_MAX_BEAM
+    assert _one(r"#define CN_MAX_PRED (\d+)", srch) == D.CN_MAX_PRED
     assert _one(r"if \(V <= S3_T \* S3_VPT && beam <= (\d+)\) \{", dec) == D.S3_MAX_BEAM
     body = dec[dec.index("const int vpt = cn_cdiv(V, S3_T);"):dec.index("#undef S3_LAUNCH")]
     assert re.sub(r"\s+", " ", body).strip() == (
@@ -94,13 +94,13 @@ def test_ffn_dispatch_matches_the_sources():
 
 
 def test_row_and_key_tiles_match_the_sources():
-    blk, ffn, ctx, dec = _src("dec_block.h"), _src("dec_ffn.h"), _src("ctx.h"), _src("decoder.hip")
+    blk, ffn, ctx, dec, rows = _src("dec_block.h"), _src("dec_ffn.h"), _src("ctx.h"), _src("decoder.hip"), _src("dec_rows.h")
     for name in ("DB_ROWS", "DB_ROWS_SP", "DB_WIDE_ROWS", "DB_WIDE_ROWS_SP", "DB_WIDE_R", "DB_NB_SELF", "DB_DEPTH_SELF", "DB_NB_CROSS",
                  "DB_DEPTH_CROSS"):
         assert _one(r"#define %s (\d+)\b" % name, blk) == getattr(D, name), name
     assert _one(r"#define DF_ROWS (\d+)", ffn) == D.DF_ROWS
     assert _one(r"#define CN_MAX_LAYERS (\d+)", ctx) == D.CN_MAX_LAYERS
-    assert _ints(r"constexpr int NB = (\d+);", dec) == {D.ATTN_NB}
+    assert _ints(r"constexpr int NB = (\d+);", rows) == {D.ATTN_NB}
     assert "if (kWide != DbOp<T>::ROWS && R >= DB_WIDE_R)" in dec
     assert "constexpr int kWide = CnIsH16<T>::value ? DB_WIDE_ROWS : DB_WIDE_ROWS_SP;" in dec
     for p in D.PRECISIONS:

@@ -4,7 +4,8 @@ operand precisions).  tests/test_cpu_decoder_geometry.py proves that the table r
 decided by margins of at least 2e-3, so the exact precisions are compared call by call without any near-tie allowance.
 
 Per geometry (a module-scoped fixture: its engines are created lazily and dropped when pytest moves to the next geometry):
-  a. search, fp32 / exact: every call's parents, tokens and order, running sums, captions, sizes and scores; greedy at beam 1
+  a. search, fp32 / exact: every call's parents, tokens and order, running sums, captions, sizes and scores; greedy at beam 1;
+     the margin planes of every call through both search-step kernels
   b. teacher-forcing logits, all four precisions x {fused step kernels, one launch per sub-layer, one pass} against the
      precision's own oracle; the 16-bit top-k of every call at the oracle's states; the sequential 16-bit search
   c. state independence, bf16 / exact: poisoned workspaces, a clip alone against the clip in its batch, eager / capture / replay
@@ -146,8 +147,39 @@ def test_search_matches_the_oracle(prec, geo):
             assert torch.equal(gr["preds"].cpu().long(), got.argmax(dim=1)), tag
 
 
+@pytest.mark.parametrize("prec", EXACT)
+def test_margins_match_the_oracle(prec, geo):
+    """The margin planes of every search (want_margins=True), through the register-resident step (its separate runner-up pass) and
+    the generic step (its k + 1-th selection round).  For every oracle call: plane 0 = the oracle's margin (last pick minus first
+    rejected candidate; infinities compare equal), plane 1 = the smallest gap between consecutive picks (+inf at k = 1), both to
+    4e-4 x (step + 1) -- each is a difference of two running sums, which test_search_matches_the_oracle holds to 2e-4 x (step + 1).
+    A (clip, step) without a call holds +inf in both planes; column max_pred of plane 0 = best minus second-best of the oracle's
+    mult_lprobs (+inf at beam 1) to 2e-4, twice the 1e-4 those scores are held to."""
+    g = geo.g
+    inf = float("inf")
+    for s in g.searches:
+        tag = (g.name, s.name, prec, D.search_kernel(g.v, s.beam))
+        ref = geo.oracle(s)
+        m = geo.decode(prec, s, want_margins=True)["margins"].numpy()
+        assert m.shape == (s.b, 2, s.max_pred + 1), tag
+        seen = set()
+        for step, clip, par, tok, sums, margin in ref["calls"]:
+            seen.add((clip, step))
+            order = min([sums[i] - sums[i + 1] for i in range(len(par) - 1)], default=inf)
+            atol = 4e-4 * (step + 1)
+            np.testing.assert_allclose(m[clip, 0, step], np.float32(margin), rtol=0, atol=atol, err_msg=str((tag, "membership", step, clip)))
+            np.testing.assert_allclose(m[clip, 1, step], np.float32(order), rtol=0, atol=atol, err_msg=str((tag, "order", step, clip)))
+        for clip in range(s.b):
+            for step in range(s.max_pred):
+                if (clip, step) not in seen:
+                    assert m[clip, 0, step] == inf and m[clip, 1, step] == inf, (tag, clip, step, m[clip, :, step])
+            lp = sorted(ref["mult_lprobs"][clip].tolist(), reverse=True)
+            final = lp[0] - lp[1] if s.beam > 1 else inf
+            np.testing.assert_allclose(m[clip, 0, s.max_pred], np.float32(final), rtol=0, atol=2e-4, err_msg=str((tag, "final", clip)))
+
+
 # ---- b. logits against the precision's own oracle -----------------------------------------------------------------------------
-MODES = ("step_fused", "step_unfused", "onepass")
+MODES =("step_fused", "step_unfused", "onepass")
 
 
 def _forcing(eng, mode, fe, lens, caps):
