@@ -150,15 +150,18 @@ __device__ __forceinline__ void cn_step_margin(float* margins, int b, int maxp, 
 // The bookkeeping of a step (beam.py:164-203), by a block of THREADS threads that has the clip's k picks in s_selv / s_self
 // (value, flat index parent * V + token) and its old state in s_prefix / s_anc / s_slot: the trace, the rows that search on
 // (n_active, live), finished hypotheses to their slot, continuing rows' prefix / anc / sum_lp / slot / cur_tok.
+// The diverse search (dec_group.h) commits one beam group at a time: the group's rows start at row `row0` of the clip (the LDS
+// arrays are passed from there, parents in s_self count from there, slots are within-clip indices) and its live-row count is
+// n_active[na]; the plain searches commit the whole clip (row0 = 0, n_active[b]).
 template <int THREADS>
 __device__ __forceinline__ void cn_search_commit(const SsArgs& a, int b, int k, int step, const float* s_selv, const int* s_self,
                                                  const int (*s_prefix)[CN_MAX_PRED + 1], const int (*s_anc)[CN_MAX_PRED],
-                                                 const int* s_slot, int* s_newpos) {
-  const int tid = threadIdx.x, V = a.V, maxp = a.maxp, rb = b * a.beam;
+                                                 const int* s_slot, int* s_newpos, const int row0 = 0, const int na = -1) {
+  const int tid = threadIdx.x, V = a.V, maxp = a.maxp, rb = b * a.beam + row0;
   if (tid < k) {
-    const size_t ti = ((size_t)step * gridDim.x + b) * a.beam + tid;
+    const size_t ti = ((size_t)step * gridDim.x + b) * a.beam + row0 + tid;
     if (a.trace_sel) {
-      a.trace_sel[2 * ti] = s_self[tid] / V;
+      a.trace_sel[2 * ti] = row0 + s_self[tid] / V;
       a.trace_sel[2 * ti + 1] = s_self[tid] % V;
     }
     if (a.trace_val) a.trace_val[ti] = s_selv[tid];
@@ -170,7 +173,7 @@ __device__ __forceinline__ void cn_search_commit(const SsArgs& a, int b, int k, 
       const bool fin = (token == a.eos_id) || (step == maxp - 1);
       s_newpos[c] = fin ? -1 : cnt++;
     }
-    a.n_active[b] = cnt;
+    a.n_active[na < 0 ? b : na] = cnt;
     if (cnt > 0) atomicAdd(&a.live[step + 1], cnt);  // rows that search on: gates the next step's kernels
   }
   __syncthreads();
@@ -179,7 +182,7 @@ __device__ __forceinline__ void cn_search_commit(const SsArgs& a, int b, int k, 
     const int parent = flat / V, token = flat % V;
     const int np = s_newpos[c];
     if (np < 0) {  // finished: write to the slot of this row position
-      const int sl = rb + s_slot[c];
+      const int sl = b * a.beam + s_slot[c];
       for (int j = tid; j <= step; j += THREADS) a.out_preds[(size_t)sl * maxp + j] = (j == step) ? token : s_prefix[parent][j + 1];
       if (tid == 0) {
         a.out_avg[sl] = s_selv[c] / (float)(step + 1);
@@ -188,7 +191,7 @@ __device__ __forceinline__ void cn_search_commit(const SsArgs& a, int b, int k, 
     } else {
       const int dst = rb + np;
       for (int j = tid; j <= step + 1; j += THREADS) a.prefix[(size_t)dst * (maxp + 1) + j] = (j == step + 1) ? token : s_prefix[parent][j];
-      for (int j = tid; j <= step; j += THREADS) a.anc[(size_t)dst * maxp + j] = (j == step) ? parent : s_anc[parent][j];
+      for (int j = tid; j <= step; j += THREADS) a.anc[(size_t)dst * maxp + j] = (j == step) ? row0 + parent : s_anc[parent][j];
       if (tid == 0) {
         a.sum_lp[dst] = s_selv[c];
         a.slot[dst] = s_slot[c];

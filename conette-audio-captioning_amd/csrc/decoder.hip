@@ -11,7 +11,7 @@
 //   * EOS floor, forbid-repeat mask, log-softmax, running sums, per-clip top-k and the
 //     finished / shrinking-k bookkeeping run in one kernel per step with no host sync.
 // This file is the host side: workspace, launch sequences, the hipGraph cache and the entry points.  The device code is in
-// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
+// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
 #include "ctx.h"
 #include <stdlib.h>
 
@@ -23,6 +23,7 @@
 #include "dec_rows.h"
 #include "dec_search.h"
 #include "dec_sample.h"
+#include "dec_group.h"
 #include "dec_align.h"
 
 #define FF2_SPLITS 8
@@ -117,6 +118,9 @@ struct DecArgs {
   float* sample_step_logits;
   float temperature, top_p;
   int top_k;
+  int n_groups, group_beam;  // conette_decode_groups: beam == n_groups * group_beam rows per clip, searched in groups (dec_group.h)
+  float diversity;
+  float* group_step_logits;  // optional
   bool operator==(const DecArgs& o) const { return memcmp(this, &o, sizeof(DecArgs)) == 0; }
 };
 
@@ -265,6 +269,12 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
                        w.kvalid, w.anc);
     CN_LAUNCH_CHECK();
   }
+  const bool grouped = a.n_groups > 0;
+  int* group_k = (int*)(a.ws + w.total);  // (B, n_groups) live rows of every group: behind the plain search's workspace
+  if (grouped) {
+    hipLaunchKernelGGL(cn_group_init_kernel, dim3(cn_cdiv(B * a.n_groups, 256)), dim3(256), 0, s, B * a.n_groups, a.group_beam, group_k);
+    CN_LAUNCH_CHECK();
+  }
   if (sampling) {  // rows never change parents: every row is its own ancestor; w.slot holds the per-row finished flag
     hipLaunchKernelGGL(cn_sample_init_kernel, dim3(64), dim3(256), 0, s, R, beam, maxp, w.anc, w.slot, a.sample_lens,
                        a.sample_tok_lp);
@@ -280,6 +290,9 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
   ss.prefix = w.prefix, ss.anc = w.anc, ss.cur_tok = w.cur_tok, ss.out_preds = a.mult_preds, ss.out_avg = a.mult_lprobs;
   ss.out_len = w.out_len, ss.trace_sel = a.trace_sel, ss.trace_val = a.trace_val, ss.live = w.live, ss.margins = a.margins;
   ss.ldv = w.ldv, ss.V = V, ss.beam = beam, ss.maxp = maxp, ss.min_pred = min_pred, ss.eos_id = cfg.eos_id, ss.dbg = db_debug;
+  GsArgs gs;  // the diverse search's own arguments: its step kernels read the groups' live rows through ss.n_active
+  gs.step_logits = a.group_step_logits, gs.G = a.n_groups, gs.W = a.group_beam, gs.lambda = a.diversity;
+  if (grouped) ss.n_active = group_k;
 
   for (int step = 0; step < maxp; ++step) {
     if (forcing) {
@@ -419,6 +432,11 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
       else if (vpt <= SM_VPT) SM_LAUNCH(8);
       else SM_LAUNCH(0);  // vocabularies beyond 8192 entries: the logits are re-read from global memory
 #undef SM_LAUNCH
+      CN_LAUNCH_CHECK();
+      continue;
+    }
+    if (grouped) {  // the groups of a clip in sequence, one launch per step (dec_group.h)
+      cn_group_step_launch(ss, gs, B, step, s);
       CN_LAUNCH_CHECK();
       continue;
     }
@@ -965,6 +983,50 @@ extern "C" int conette_sample(conette_ctx* ctx, const float* frame_embs, const i
   a.temperature = temperature, a.top_p = top_p, a.top_k = top_k;
   // (eager: the caller's output buffers usually change from call to call, which a graph cache keyed on them would only churn
   //  through; the launch sequence is static and holds no host state, so the caller may capture it)
+  CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
+}
+
+// ---- diverse beam search (dec_group.h): the step path with the groups' sequential top-k in place of the search step ----
+static bool groups_shape_ok(int32_t n_groups, int32_t group_beam) {
+  return n_groups >= 1 && group_beam >= 1 && n_groups <= CN_MAX_BEAM && group_beam <= CN_MAX_BEAM && n_groups * group_beam <= CN_MAX_BEAM;
+}
+extern "C" size_t conette_decode_groups_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t n_groups,
+                                                        int32_t group_beam, int32_t max_pred) {
+  if (!ctx || batch <= 0 || t_audio <= 0 || max_pred <= 0 || !groups_shape_ok(n_groups, group_beam)) return 0;
+  return conette_decode_workspace_bytes(ctx, batch, t_audio, n_groups * group_beam, max_pred) + cn_align((size_t)batch * n_groups * 4);
+}
+
+extern "C" int conette_decode_groups(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                                     const uint8_t* forbid_mask, int32_t batch, int32_t t_audio, int32_t n_groups,
+                                     int32_t group_beam, float diversity_penalty, int32_t min_pred, int32_t max_pred,
+                                     int32_t* best_preds, float* best_lprobs, int32_t* mult_preds, float* mult_lprobs,
+                                     int32_t* out_sizes, int32_t* trace_sel, float* trace_val, float* step_logits, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (!ctx || !frame_embs || !frame_lens || !bos_ids || !best_preds || !best_lprobs || !mult_preds || !mult_lprobs ||
+      !out_sizes || !workspace || batch <= 0 || t_audio <= 0) {
+    cn_set_error("decode_groups: bad argument");
+    return CN_ERR_ARG;
+  }
+  if (!groups_shape_ok(n_groups, group_beam)) {
+    cn_set_error("decode_groups: n_groups=%d x group_beam=%d unsupported (both >= 1, product <= %d)", n_groups, group_beam, CN_MAX_BEAM);
+    return CN_ERR_ARG;
+  }
+  if (!(diversity_penalty >= 0.f) || !(diversity_penalty < INFINITY)) {
+    cn_set_error("decode_groups: diversity_penalty=%g must be finite and >= 0", (double)diversity_penalty);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_model(ctx, "decode_groups", max_pred, min_pred, "decode_groups: max_pred=%d (1..%d) min_pred=%d unsupported", max_pred,
+                         CN_MAX_PRED, min_pred));
+  CN_TRY(dec_check_workspace("decode_groups", workspace_bytes,
+                             conette_decode_groups_workspace_bytes(ctx, batch, t_audio, n_groups, group_beam, max_pred)));
+  DecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.bos_ids = bos_ids, a.forbid = forbid_mask, a.ws = (char*)workspace;
+  a.best_preds = best_preds, a.best_lprobs = best_lprobs, a.mult_preds = mult_preds, a.mult_lprobs = mult_lprobs;
+  a.out_sizes = out_sizes, a.trace_sel = trace_sel, a.trace_val = trace_val;
+  a.B = batch, a.Ta = t_audio, a.beam = n_groups * group_beam, a.min_pred = min_pred, a.maxp = max_pred;
+  a.n_groups = n_groups, a.group_beam = group_beam, a.diversity = diversity_penalty, a.group_step_logits = step_logits;
+  // (eager, as conette_sample: the launch sequence is static and holds no host state, so the caller may capture it)
   CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
 }
 

@@ -33,7 +33,7 @@ EXPORTS = (
     "conette_stream_destroy", "conette_forcing_workspace_bytes", "conette_forcing",
     "conette_greedy_workspace_bytes", "conette_greedy", "conette_decode_graph_nodes", "conette_encode_nonfinite",
     "conette_score_workspace_bytes", "conette_score", "conette_sample_workspace_bytes", "conette_sample",
-    "conette_align_workspace_bytes", "conette_align",
+    "conette_align_workspace_bytes", "conette_align", "conette_decode_groups_workspace_bytes", "conette_decode_groups",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -154,6 +154,12 @@ def load_library() -> C.CDLL:
     lib.conette_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_decode_groups_workspace_bytes.restype = C.c_size_t
+    lib.conette_decode_groups_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_decode_groups.restype = C.c_int
+    lib.conette_decode_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.conette_greedy_workspace_bytes.restype = C.c_size_t
     lib.conette_greedy_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.conette_greedy.restype = C.c_int
@@ -762,6 +768,44 @@ class Engine:
                if parts[0][k] is not None}
         out["sizes"] = torch.stack([p["sizes"] for p in parts]).amax(dim=0)
         return out
+
+    def decode_groups(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, bos_ids: torch.Tensor,
+                      forbid_mask: Optional[torch.Tensor], n_groups: int, group_beam: int, diversity_penalty: float, min_pred: int,
+                      max_pred: int, want_trace: bool = False, want_logits: bool = False) -> Dict[str, torch.Tensor]:
+        """Diverse beam search (conette_decode_groups, include/conette_hip.h; the rule: group_search.py): ``n_groups`` groups of
+        ``group_beam`` beams per clip, a group's candidates paying ``diversity_penalty`` for each time their token was already
+        picked at this step by an earlier group.  Returns ``decode``'s outputs at beam G * W -- "best_preds", "best_lprobs",
+        "mult_preds" (B, G * W, max_pred) and "mult_lprobs" (B, G * W) in slot order, group-major, "sizes" -- [, "trace_sel"
+        (max_pred, B, G * W, 2), "trace_val" (max_pred, B, G * W)] [, "step_logits" (max_pred, B * G * W, vocab), the raw logits
+        each step decided on].  Scores are the model's averaged log-probabilities, never the penalised keys."""
+        from . import group_search
+        g, w = group_search.check_arguments(n_groups, group_beam, diversity_penalty)
+        b, t, _ = frame_embs.shape
+        max_pred, r = int(max_pred), b * g * w
+        fe = frame_embs.to(self.device, torch.float32).contiguous()
+        lens_in = frame_lens.to(self.device, torch.int32).contiguous()
+        bos = bos_ids.to(self.device, torch.int32).contiguous()
+        fm = None
+        if forbid_mask is not None:
+            if forbid_mask.numel() != self.vocab_size:
+                raise ValueError("forbid_mask must have vocab_size entries")
+            fm = forbid_mask.to(self.device, torch.uint8).contiguous()
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        o = {"best_preds": e((b, max_pred), torch.int32), "best_lprobs": e((b,), torch.float32),
+             "mult_preds": e((b, g * w, max_pred), torch.int32), "mult_lprobs": e((b, g * w), torch.float32),
+             "sizes": e((2,), torch.int32),
+             "trace_sel": e((max_pred, b, g * w, 2), torch.int32) if want_trace else None,
+             "trace_val": e((max_pred, b, g * w), torch.float32) if want_trace else None,
+             "step_logits": e((max_pred, r, self.vocab_size), torch.float32) if want_logits else None}
+        ctx = self._ctx_dec
+        need = self.lib.conette_decode_groups_workspace_bytes(ctx, b, t, g, w, max_pred)
+        wsb = self._workspace("dec", need)
+        st = self.lib.conette_decode_groups(ctx, _ptr(fe), _ptr(lens_in), _ptr(bos), _ptr(fm), b, t, g, w, float(diversity_penalty),
+                                            int(min_pred), max_pred, _ptr(o["best_preds"]), _ptr(o["best_lprobs"]),
+                                            _ptr(o["mult_preds"]), _ptr(o["mult_lprobs"]), _ptr(o["sizes"]), _ptr(o["trace_sel"]),
+                                            _ptr(o["trace_val"]), _ptr(o["step_logits"]), _ptr(wsb), wsb.numel(), _stream())
+        _check(st, "conette_decode_groups")
+        return {k: v for k, v in o.items() if v is not None}
 
     def decode_input_buffer(self, b: int, t: int, beam: int, max_pred: int, slot: int = 0, margins: bool = False,
                             exact: bool = False) -> torch.Tensor:

@@ -412,6 +412,54 @@ class CoNeTTEModel:
                 outs["tags"] = probs_to_names(clip_probs, 0.3, self.audioset_idx_to_name)
             return outs
 
+    @torch.no_grad()
+    def caption_diverse(self, x, num_groups: int = 3, group_beam_size: int = 1, diversity_penalty: float = 0.5, sr=None,
+                        x_shapes=None, preprocess: bool = True, task: Union[str, List[str], None] = None,
+                        min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
+                        forbid_rep_mode: Optional[str] = None, threshold: Union[float, Tensor] = 0.3) -> Dict[str, Any]:
+        """``num_groups * group_beam_size`` deterministic, likely and DIFFERENT captions per clip: diverse beam search on the
+        device (conette_decode_groups; the rule: group_search.py) -- the search runs in ``num_groups`` groups of
+        ``group_beam_size`` beams, a group's candidates paying ``diversity_penalty`` for each time their token was already
+        picked at this step by an earlier group.  ``x``, ``task`` and the size / mask arguments as in ``forward``, whose keys it
+        returns: "mult_preds" (B, G * W, pred_size), "mult_cands" and "mult_lprobs" (B, G * W) hold the hypotheses group-major
+        (group g at positions g * W .. g * W + W - 1), "preds" / "cands" / "lprobs" the one with the highest mean log-probability;
+        the scores are the model's, never the penalised keys.  ``num_groups=1`` is ``forward`` at ``beam_size=group_beam_size``.
+        Precision "certified*" and the mixed precisions run this search on the base pipeline's decoder context, with no exact
+        re-run: no certificate is defined for it.  With waveforms in, an overflow of the 16-bit encoders' fp16 residual stream
+        raises as in ``sample``."""
+        from . import group_search
+        g, w = group_search.check_arguments(num_groups, group_beam_size, diversity_penalty)
+        with torch.cuda.device(self.device):
+            keep: dict = {}
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess, keep)
+            audio_shape = torch.as_tensor(audio_shape)
+            clip_probs = keep.get("clip_probs")
+            bsize = len(audio)
+            tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
+            if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
+                bad = self.engine.encode_nonfinite()       # (include/conette_hip.h: conette_encode_nonfinite)
+                if bad:
+                    raise RuntimeError(
+                        f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
+                        "positions with non-finite LayerNorm statistics); use precision='exact' or 'fp32' for this checkpoint")
+            cfg = self.config
+            min_pred = cfg.min_pred_size if min_pred_size is None else int(min_pred_size)
+            max_pred = cfg.max_pred_size if max_pred_size is None else int(max_pred_size)
+            res = self.engine.decode_groups(audio, audio_shape[:, 1].to(torch.int32), self.batch_to_task_token_ids(dataset_lst, source_lst),
+                                            self.get_forbid_rep_mask(forbid_rep_mode), g, w, float(diversity_penalty), min_pred, max_pred)
+            pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())            # the one host sync
+            mult_preds = res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous()
+            preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()
+            outs = {
+                "cands": self.tokenizer.decode_rec(preds), "preds": preds, "lprobs": res["best_lprobs"],
+                "mult_cands": self.tokenizer.decode_rec(mult_preds), "mult_preds": mult_preds, "mult_lprobs": res["mult_lprobs"],
+                "tasks": tasks,
+            }
+            if clip_probs is not None:
+                outs["tags_probs"] = clip_probs
+                outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
+            return outs
+
     def teacher_forcing(self, x, caps_in: Tensor, sr=None, x_shapes=None, preprocess: bool = True) -> Tensor:
         """CoNeTTEPLM.decode_audio(encode_audio(...), "forcing", caps_in=caps_in) (pl_modules/conette.py:392-417,
         nn/decoding/forcing.py:12-71): logits (B, vocab, cap_len) of given input captions in one causal pass.

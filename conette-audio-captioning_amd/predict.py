@@ -4,6 +4,7 @@
     python -m conette_amd.predict --audio a.wav b.wav --task clotho --model_name DIR_OR_HUB_NAME \
         [--csv_export out.csv] [--precision certified|certified:BASE|bf16|bf16+f16dec|f16|mixed|mixed16|exact|fp32]
         [--sample N --temperature T --top_k K --top_p P --seed S] [--align]
+        [--beam_groups G --group_beam W --diversity_penalty L]
 
 ``--model_path`` (a Lightning training log directory with hydra/config.yaml + checkpoints/best.ckpt, predict.py:123-178) is
 accepted when the audio encoder's weights come with it: the reference builds its HF wrapper around the Lightning module and leaves
@@ -58,12 +59,23 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
                              "where in the clip the decoder listens while it predicts the word (CoNeTTEModel.align_captions).")
     parser.add_argument("--align_mass", type=float, default=0.5,
                         help="With --align: start .. end is the shortest window holding this share of the word's attention.")
+    parser.add_argument("--beam_groups", type=int, default=0,
+                        help="G > 0: diverse beam search in G groups (CoNeTTEModel.caption_diverse): G x --group_beam different captions "
+                             "per file, one row each, group-major.")
+    parser.add_argument("--group_beam", type=int, help="With --beam_groups: beams per group.", default=1)
+    parser.add_argument("--diversity_penalty", type=float, default=0.5,
+                        help="With --beam_groups: what a candidate pays for each earlier group that picked its token at this step.")
     parser.add_argument("--csv_export", type=_opt_str, help="Path to CSV output file.", default=None)
     parser.add_argument("--verbose", type=int, help="Verbose level.", default=1)
     parser.add_argument("--precision", type=str, default=None,
                         help="certified (default: fp16 pipeline + id certificate, uncertified clips re-run exactly), certified:<base>, "
                              "bf16, bf16+f16dec, f16, mixed, mixed16, exact, fp32")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.beam_groups > 0 and args.sample > 0:
+        raise ValueError("--beam_groups searches for different captions; it does not go with --sample")
+    if args.beam_groups > 0 and args.align:
+        raise ValueError("--align places the words of the searched caption; it does not go with --beam_groups")
+    return args
 
 
 def format_results(fpaths: List[str], tasks: List[str], cands: List[str]) -> List[dict]:
@@ -179,7 +191,13 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         if args.csv_export is not None:
             write_csv(args.csv_export, results)
         return results
-    if args.sample > 0:   # N draws per file, in the order drawn
+    if args.beam_groups > 0:   # G x W captions per file, group-major
+        outs = model.caption_diverse(fpaths, num_groups=args.beam_groups, group_beam_size=args.group_beam,
+                                     diversity_penalty=args.diversity_penalty, task=tasks)
+        n = args.beam_groups * args.group_beam
+        results = format_results([f for f in fpaths for _ in range(n)], [t for t in outs["tasks"] for _ in range(n)],
+                                 [c for cands in outs["mult_cands"] for c in cands])
+    elif args.sample > 0:   # N draws per file, in the order drawn
         outs = model.sample(fpaths, num_samples=args.sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                             seed=args.seed, task=tasks)
         results = format_results([f for f in fpaths for _ in range(args.sample)], [t for t in outs["tasks"] for _ in range(args.sample)],

@@ -264,6 +264,47 @@ int conette_sample(conette_ctx* ctx, const float* frame_embs, const int32_t* fra
                    float* sum_lprobs, int32_t* lens, int32_t* out_sizes, float* tok_lprobs, float* step_logits,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Diverse beam search (Vijayakumar et al. 2016; Hugging Face's num_beam_groups / diversity_penalty): n_groups * group_beam
+ * deterministic, likely and DIFFERENT captions per clip, on the KV-cached step path of conette_decode with one search step per
+ * decode step that goes through the clip's groups in sequence (csrc/dec_group.h; the CPU restatement of the rule is
+ * conette_amd/group_search.py).  G = n_groups, W = group_beam, lambda = diversity_penalty.
+ *   rows       clip b owns rows b * G * W ..; group g owns rows g * W .. g * W + W - 1 of the clip, its k_g live rows (W at the
+ *              start) compacted to the front of its own range; a row's ancestors never leave its group
+ *   one step i of a clip, groups g = 0 .. G - 1 in this order; a group with k_g == 0 takes no picks and adds nothing to the counts:
+ *     candidates  the group's live rows (step 0: its first row only); logits masked as conette_decode masks them (EOS floor while
+ *                 i < min_pred, forbid-repeat over the row's own prefix, position 0 included); lp = log_softmax of the masked
+ *                 row, (z - max) - log(sum), in fp32
+ *     model score m(p, v) = sum_lp[p] + lp[p][v] (step 0: lp)
+ *     counts      c[v] = the number of picks made AT THIS STEP by groups 0 .. g - 1 of this clip whose token is v; every pick
+ *                 counts, those that finish included
+ *     key         s(p, v) = m if c[v] == 0, else m - lambda * c[v]: one rounded fp32 multiply, then one rounded fp32 subtract
+ *     picks       the top k_g keys over the group's k_g * V candidates; ties go to the lowest flat index p_in_group * V + v
+ *     carried     a pick carries its MODEL SCORE m, never its key: running sums and returned scores are the model's
+ *                 log-probabilities of the caption
+ *     bookkeeping conette_decode's, per group: a pick of <eos>, or any pick at step max_pred - 1, goes to output slot
+ *                 g * W + (the slot of its row) with score m / (i + 1) and leaves; the others continue with a smaller k_g
+ * Outputs as conette_decode's with beam = G * W: mult_preds (B, G * W, max_pred) / mult_lprobs (B, G * W) in slot order, group-major;
+ * best_* = the first maximum of the averaged score over all G * W slots; out_sizes; no `margins` (no certificate is defined for
+ * this search) and no step0_logits.
+ *   trace_sel   : optional dev (max_pred, B, G * W, 2) int32 = (within-clip parent row, token) of the picks of group g at positions
+ *                 g * W + pick, in descending key order, -1 where unused; or NULL
+ *   trace_val   : optional dev (max_pred, B, G * W) fp32, the carried model sums of those picks
+ *   step_logits : optional dev (max_pred, B * G * W, vocab) fp32, the RAW (unmasked) logits of the rows as they stood when that
+ *                 step decided; the rows of a clip all of whose groups have finished are unspecified; or NULL
+ * With n_groups == 1 the search is conette_decode at beam group_beam, bit for bit, for any lambda; group 0 is that search for any
+ * G and lambda, and with lambda == 0 every group is (on equal logits: the decoder runs G * W rows per clip, not W).
+ * n_groups >= 1, group_beam >= 1, n_groups * group_beam <= 16 (up to 8 with vocab <= 8192 on the register-resident kernel, beyond
+ * on the generic one), diversity_penalty finite and >= 0, max_pred <= 64.  The workspace is conette_decode's at beam G * W plus the
+ * groups' counters.  Asynchronous on `stream`, capturable, never replayed from the decode graph cache; results are bit-identical
+ * from run to run.  Works on decoder-only contexts and in every precision. */
+size_t conette_decode_groups_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t n_groups,
+                                             int32_t group_beam, int32_t max_pred);
+int conette_decode_groups(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                          const uint8_t* forbid_mask, int32_t batch, int32_t t_audio, int32_t n_groups, int32_t group_beam,
+                          float diversity_penalty, int32_t min_pred, int32_t max_pred, int32_t* best_preds, float* best_lprobs,
+                          int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes, int32_t* trace_sel, float* trace_val,
+                          float* step_logits, void* workspace, size_t workspace_bytes, void* stream);
+
 /* a1: torchaudio.functional.resample (preprocessor.py:134-141), sinc_interpolation width 6,
  * rolloff 0.99.  in: dev (rows, n_in) fp32; out: dev (rows, n_out), n_out = ceil(n_in*new/orig). */
 int conette_resample(const float* in, int32_t rows, int32_t n_in, int32_t orig_sr, int32_t new_sr, float* out,
