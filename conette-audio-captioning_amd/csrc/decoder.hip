@@ -11,7 +11,7 @@
 //   * EOS floor, forbid-repeat mask, log-softmax, running sums, per-clip top-k and the
 //     finished / shrinking-k bookkeeping run in one kernel per step with no host sync.
 // This file is the host side: workspace, launch sequences, the hipGraph cache and the entry points.  The device code is in
-// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
+// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_constrain.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
 #include "ctx.h"
 #include <stdlib.h>
 
@@ -24,6 +24,7 @@
 #include "dec_search.h"
 #include "dec_sample.h"
 #include "dec_group.h"
+#include "dec_constrain.h"
 #include "dec_align.h"
 
 #define FF2_SPLITS 8
@@ -121,6 +122,12 @@ struct DecArgs {
   int n_groups, group_beam;  // conette_decode_groups: beam == n_groups * group_beam rows per clip, searched in groups (dec_group.h)
   float diversity;
   float* group_step_logits;  // optional
+  int constrained;           // conette_decode_constrained: the steered search at beam `beam` (dec_constrain.h)
+  int prefix_width, no_repeat_ngram;
+  const int32_t* prefix;       // these four are optional
+  const int32_t* prefix_lens;
+  const uint8_t* ban;
+  float* constrain_step_logits;
   bool operator==(const DecArgs& o) const { return memcmp(this, &o, sizeof(DecArgs)) == 0; }
 };
 
@@ -293,6 +300,9 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
   GsArgs gs;  // the diverse search's own arguments: its step kernels read the groups' live rows through ss.n_active
   gs.step_logits = a.group_step_logits, gs.G = a.n_groups, gs.W = a.group_beam, gs.lambda = a.diversity;
   if (grouped) ss.n_active = group_k;
+  CsArgs cs;  // the constrained search's own arguments
+  cs.prefix = a.prefix, cs.prefix_lens = a.prefix_lens, cs.ban = a.ban, cs.step_logits = a.constrain_step_logits;
+  cs.P = a.prefix_width, cs.ngram = a.no_repeat_ngram;
 
   for (int step = 0; step < maxp; ++step) {
     if (forcing) {
@@ -437,6 +447,11 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
     }
     if (grouped) {  // the groups of a clip in sequence, one launch per step (dec_group.h)
       cn_group_step_launch(ss, gs, B, step, s);
+      CN_LAUNCH_CHECK();
+      continue;
+    }
+    if (a.constrained) {  // the steered step, one launch per step (dec_constrain.h)
+      cn_constrain_step_launch(ss, cs, B, step, s);
       CN_LAUNCH_CHECK();
       continue;
     }
@@ -1026,6 +1041,58 @@ extern "C" int conette_decode_groups(conette_ctx* ctx, const float* frame_embs, 
   a.out_sizes = out_sizes, a.trace_sel = trace_sel, a.trace_val = trace_val;
   a.B = batch, a.Ta = t_audio, a.beam = n_groups * group_beam, a.min_pred = min_pred, a.maxp = max_pred;
   a.n_groups = n_groups, a.group_beam = group_beam, a.diversity = diversity_penalty, a.group_step_logits = step_logits;
+  // (eager, as conette_sample: the launch sequence is static and holds no host state, so the caller may capture it)
+  CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
+}
+
+// ---- constrained beam search (dec_constrain.h): the step path with the steered step in place of the search step ----
+extern "C" size_t conette_decode_constrained_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t beam,
+                                                             int32_t max_pred) {
+  if (!ctx || batch <= 0 || t_audio <= 0 || max_pred <= 0 || beam < 1 || beam > CN_MAX_BEAM) return 0;
+  return conette_decode_workspace_bytes(ctx, batch, t_audio, beam, max_pred);  // (the step keeps nothing of its own between launches)
+}
+
+extern "C" int conette_decode_constrained(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                                          const uint8_t* forbid_mask, const int32_t* prefix, const int32_t* prefix_lens,
+                                          int32_t prefix_width, const uint8_t* ban_mask, int32_t no_repeat_ngram, int32_t batch,
+                                          int32_t t_audio, int32_t beam, int32_t min_pred, int32_t max_pred, int32_t* best_preds,
+                                          float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
+                                          int32_t* trace_sel, float* trace_val, float* step_logits, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  if (!ctx || !frame_embs || !frame_lens || !bos_ids || !best_preds || !best_lprobs || !mult_preds || !mult_lprobs ||
+      !out_sizes || !workspace || batch <= 0 || t_audio <= 0) {
+    cn_set_error("decode_constrained: bad argument");
+    return CN_ERR_ARG;
+  }
+  if (beam < 1 || beam > CN_MAX_BEAM) {
+    cn_set_error("decode_constrained: beam=%d unsupported (1..%d)", beam, CN_MAX_BEAM);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_model(ctx, "decode_constrained", max_pred, min_pred, "decode_constrained: max_pred=%d (1..%d) min_pred=%d unsupported",
+                         max_pred, CN_MAX_PRED, min_pred));
+  if (prefix_width < 0 || prefix_width > max_pred - 1) {
+    cn_set_error("decode_constrained: prefix_width=%d outside 0 .. max_pred - 1 = %d", prefix_width, max_pred - 1);
+    return CN_ERR_ARG;
+  }
+  if (prefix_width > 0 && (!prefix || !prefix_lens)) {
+    cn_set_error("decode_constrained: prefix and prefix_lens must be given with prefix_width=%d > 0", prefix_width);
+    return CN_ERR_ARG;
+  }
+  if (no_repeat_ngram < 0 || no_repeat_ngram > CN_MAX_NGRAM) {
+    cn_set_error("decode_constrained: no_repeat_ngram=%d outside 0 .. %d", no_repeat_ngram, CN_MAX_NGRAM);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_workspace("decode_constrained", workspace_bytes,
+                             conette_decode_constrained_workspace_bytes(ctx, batch, t_audio, beam, max_pred)));
+  DecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.bos_ids = bos_ids, a.forbid = forbid_mask, a.ws = (char*)workspace;
+  a.best_preds = best_preds, a.best_lprobs = best_lprobs, a.mult_preds = mult_preds, a.mult_lprobs = mult_lprobs;
+  a.out_sizes = out_sizes, a.trace_sel = trace_sel, a.trace_val = trace_val;
+  a.B = batch, a.Ta = t_audio, a.beam = beam, a.min_pred = min_pred, a.maxp = max_pred;
+  a.constrained = 1, a.prefix_width = prefix_width, a.no_repeat_ngram = no_repeat_ngram;
+  if (prefix_width > 0) a.prefix = prefix, a.prefix_lens = prefix_lens;
+  a.ban = ban_mask, a.constrain_step_logits = step_logits;
   // (eager, as conette_sample: the launch sequence is static and holds no host state, so the caller may capture it)
   CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
 }

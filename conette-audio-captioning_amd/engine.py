@@ -34,6 +34,7 @@ EXPORTS = (
     "conette_greedy_workspace_bytes", "conette_greedy", "conette_decode_graph_nodes", "conette_encode_nonfinite",
     "conette_score_workspace_bytes", "conette_score", "conette_sample_workspace_bytes", "conette_sample",
     "conette_align_workspace_bytes", "conette_align", "conette_decode_groups_workspace_bytes", "conette_decode_groups",
+    "conette_decode_constrained_workspace_bytes", "conette_decode_constrained",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -160,6 +161,13 @@ def load_library() -> C.CDLL:
     lib.conette_decode_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_decode_constrained_workspace_bytes.restype = C.c_size_t
+    lib.conette_decode_constrained_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_decode_constrained.restype = C.c_int
+    lib.conette_decode_constrained.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.conette_greedy_workspace_bytes.restype = C.c_size_t
     lib.conette_greedy_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.conette_greedy.restype = C.c_int
@@ -805,6 +813,70 @@ class Engine:
                                             _ptr(o["mult_preds"]), _ptr(o["mult_lprobs"]), _ptr(o["sizes"]), _ptr(o["trace_sel"]),
                                             _ptr(o["trace_val"]), _ptr(o["step_logits"]), _ptr(wsb), wsb.numel(), _stream())
         _check(st, "conette_decode_groups")
+        return {k: v for k, v in o.items() if v is not None}
+
+    def decode_constrained(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, bos_ids: torch.Tensor,
+                           forbid_mask: Optional[torch.Tensor], beam: int, min_pred: int, max_pred: int,
+                           prefix: Optional[torch.Tensor] = None, prefix_lens: Optional[torch.Tensor] = None,
+                           ban_mask: Optional[torch.Tensor] = None, no_repeat_ngram: int = 0, want_trace: bool = False,
+                           want_logits: bool = False, exact: bool = False, check: bool = True) -> Dict[str, torch.Tensor]:
+        """Constrained beam search (conette_decode_constrained, include/conette_hip.h; the rule: constrained_search.py): the beam
+        search at ``beam`` whose captions begin with ``prefix`` (B, P) int [``prefix_lens`` (B,); None: every row is P long], never
+        hold a token of ``ban_mask`` (vocab) and repeat no ``no_repeat_ngram``-gram.  Returns ``decode``'s outputs -- a void slot
+        has ``mult_lprobs`` -inf and pad throughout -- [, "trace_sel" (max_pred, B, beam, 2), "trace_val" (max_pred, B, beam)]
+        [, "step_logits" (max_pred, B * beam, vocab), the raw logits each step decided on].  ``check``: the prefix tokens are
+        checked on the host (in the vocabulary, neither <eos> nor pad; a device prefix is copied back for it); ``exact``
+        (certified engines only): run on the exact context."""
+        from . import constrained_search
+        b, t, _ = frame_embs.shape
+        max_pred = int(max_pred)
+        pw = 0 if prefix is None else int(prefix.shape[1])
+        if prefix is not None and (prefix.dim() != 2 or prefix.shape[0] != b):
+            raise ValueError(f"prefix must be (batch, P), got {tuple(prefix.shape)}")
+        w, n = constrained_search.check_arguments(beam, no_repeat_ngram, max_pred, pw)
+        ctx = self._ctx_dec
+        if exact:
+            if self._ctx_x is None:
+                raise RuntimeError("decode_constrained(exact=True) needs a certified engine")
+            ctx = self._ctx_x
+        pre = plens = None
+        if pw > 0:
+            if prefix_lens is None:
+                prefix_lens = torch.full((b,), pw, dtype=torch.int32)
+            if prefix_lens.numel() != b:
+                raise ValueError("prefix_lens must have one entry per clip")
+            if check:
+                ph, lh = prefix.cpu().long(), prefix_lens.cpu().long()
+                if bool(((lh < 0) | (lh > pw)).any()):
+                    raise ValueError(f"prefix_lens must lie in 0 .. {pw}")
+                live = ph[torch.arange(pw)[None] < lh[:, None]]
+                if bool(((live < 0) | (live >= self.vocab_size) | (live == self.eos_id) | (live == self.pad_id)).any()):
+                    raise ValueError("prefix tokens must lie in the vocabulary and be neither <eos> nor pad")
+            pre = prefix.to(self.device, torch.int32).contiguous()
+            plens = prefix_lens.to(self.device, torch.int32).contiguous()
+        fe = frame_embs.to(self.device, torch.float32).contiguous()
+        lens_in = frame_lens.to(self.device, torch.int32).contiguous()
+        bos = bos_ids.to(self.device, torch.int32).contiguous()
+        masks = []
+        for name, m in (("forbid_mask", forbid_mask), ("ban_mask", ban_mask)):
+            if m is not None and m.numel() != self.vocab_size:
+                raise ValueError(f"{name} must have vocab_size entries")
+            masks.append(None if m is None else m.to(self.device, torch.uint8).contiguous())
+        fm, bm = masks
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        o = {"best_preds": e((b, max_pred), torch.int32), "best_lprobs": e((b,), torch.float32),
+             "mult_preds": e((b, w, max_pred), torch.int32), "mult_lprobs": e((b, w), torch.float32),
+             "sizes": e((2,), torch.int32),
+             "trace_sel": e((max_pred, b, w, 2), torch.int32) if want_trace else None,
+             "trace_val": e((max_pred, b, w), torch.float32) if want_trace else None,
+             "step_logits": e((max_pred, b * w, self.vocab_size), torch.float32) if want_logits else None}
+        need = self.lib.conette_decode_constrained_workspace_bytes(ctx, b, t, w, max_pred)
+        wsb = self._workspace("xdec" if exact else "dec", need)
+        st = self.lib.conette_decode_constrained(ctx, _ptr(fe), _ptr(lens_in), _ptr(bos), _ptr(fm), _ptr(pre), _ptr(plens), pw, _ptr(bm),
+                                                 n, b, t, w, int(min_pred), max_pred, _ptr(o["best_preds"]), _ptr(o["best_lprobs"]),
+                                                 _ptr(o["mult_preds"]), _ptr(o["mult_lprobs"]), _ptr(o["sizes"]), _ptr(o["trace_sel"]),
+                                                 _ptr(o["trace_val"]), _ptr(o["step_logits"]), _ptr(wsb), wsb.numel(), _stream())
+        _check(st, "conette_decode_constrained")
         return {k: v for k, v in o.items() if v is not None}
 
     def decode_input_buffer(self, b: int, t: int, beam: int, max_pred: int, slot: int = 0, margins: bool = False,

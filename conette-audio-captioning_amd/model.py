@@ -460,6 +460,105 @@ class CoNeTTEModel:
                 outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
             return outs
 
+    def _prefix_rows(self, prefix, bsize: int) -> List[List[int]]:
+        """one token list per clip from ``caption_constrained``'s ``prefix``: None, one string, one string per clip, or padded ids"""
+        if prefix is None:
+            return [[] for _ in range(bsize)]
+        if isinstance(prefix, str):
+            return [self.tokenizer.words_to_ids(prefix)] * bsize
+        if isinstance(prefix, (list, tuple)) and all(isinstance(p, str) for p in prefix):
+            if len(prefix) != bsize:
+                raise ValueError(f"prefix holds {len(prefix)} strings for {bsize} clips")
+            return [self.tokenizer.words_to_ids(p) for p in prefix]
+        ids = torch.as_tensor(prefix)
+        if ids.ndim != 2 or ids.shape[0] != bsize or ids.is_floating_point():
+            raise ValueError("prefix must be a string, one string per clip, or an integer tensor of shape (bsize, P) padded with pad_id")
+        pad = self.tokenizer.pad_token_id
+        rows = []
+        for r in ids.tolist():
+            n = len(r)
+            while n > 0 and r[n - 1] == pad:
+                n -= 1
+            rows.append([int(t) for t in r[:n]])
+        return rows
+
+    @torch.no_grad()
+    def caption_constrained(self, x, prefix=None, banned=None, no_repeat_ngram_size: int = 0, beam_size: Optional[int] = None, sr=None,
+                            x_shapes=None, preprocess: bool = True, task: Union[str, List[str], None] = None,
+                            min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
+                            forbid_rep_mode: Optional[str] = None, threshold: Union[float, Tensor] = 0.3) -> Dict[str, Any]:
+        """The beam search of ``forward``, steered on the device (conette_decode_constrained; the rule: constrained_search.py):
+        every caption begins with ``prefix`` -- one string for all clips, one string per clip, or ids (B, P) right-padded with
+        pad_id --, never holds a token of ``banned`` (words or ids) and repeats no ``no_repeat_ngram_size``-gram (0: off; the task
+        token takes part).  Strings go through ``AACTokenizer.words_to_ids``: whitespace-separated vocabulary entries, not the
+        reference's spaCy tokenisation.  A prefix word outside the vocabulary raises a ValueError that names it; a banned word
+        outside the vocabulary is ignored.  ValueError also for a prefix that contains <eos> / <pad> / <bos> or a banned token,
+        repeats a token the forbid mask allows once or an n-gram of its own, or is not shorter than ``max_pred_size``, and for a
+        ban of <eos>.  Returns ``forward``'s keys; scores are the model's mean log-probabilities, prefix tokens included; a
+        hypothesis slot the constraints left empty has ``mult_lprobs`` -inf and an empty caption.  Precision "certified*" and
+        the mixed precisions run this search on the base pipeline's decoder context, with no exact re-run: no certificate is
+        defined for it.  With waveforms in, an overflow of the 16-bit encoders' fp16 residual stream raises as in ``sample``."""
+        from . import constrained_search
+        with torch.cuda.device(self.device):
+            keep: dict = {}
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess, keep)
+            audio_shape = torch.as_tensor(audio_shape)
+            clip_probs = keep.get("clip_probs")
+            bsize = len(audio)
+            tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
+            if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
+                bad = self.engine.encode_nonfinite()       # (include/conette_hip.h: conette_encode_nonfinite)
+                if bad:
+                    raise RuntimeError(
+                        f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
+                        "positions with non-finite LayerNorm statistics); use precision='exact' or 'fp32' for this checkpoint")
+            cfg, tok = self.config, self.tokenizer
+            beam = cfg.beam_size if beam_size is None else int(beam_size)
+            min_pred = cfg.min_pred_size if min_pred_size is None else int(min_pred_size)
+            max_pred = cfg.max_pred_size if max_pred_size is None else int(max_pred_size)
+            vocab = self.engine.vocab_size
+            ban = None
+            if banned is not None:
+                items = [banned] if isinstance(banned, (str, int)) else (banned.tolist() if isinstance(banned, Tensor) else list(banned))
+                ids = [t for it in items for t in (tok.words_to_ids(it, skip_unknown=True) if isinstance(it, str) else [int(it)])]
+                if any(not 0 <= t < vocab for t in ids):
+                    raise ValueError(f"banned ids must lie in 0 .. {vocab - 1}")
+                if tok.eos_token_id in ids:
+                    raise ValueError("<eos> cannot be banned: no caption could end")
+                if ids:
+                    ban = torch.zeros(vocab, dtype=torch.bool)
+                    ban[torch.as_tensor(ids)] = True
+            rows = self._prefix_rows(prefix, bsize)
+            width = max(len(r) for r in rows)
+            w, n = constrained_search.check_arguments(beam, no_repeat_ngram_size, max_pred, width)
+            forbid = self.get_forbid_rep_mask(forbid_rep_mode)
+            bos = self.batch_to_task_token_ids(dataset_lst, source_lst)
+            fb_host = None if forbid is None else forbid.cpu().numpy()
+            for r, t in zip(rows, bos.tolist()):
+                constrained_search.check_prefix(r, int(t), vocab_size=vocab, max_pred=max_pred, eos_id=tok.eos_token_id,
+                                                pad_id=tok.pad_token_id, bos_id=tok.bos_token_id,
+                                                ban=None if ban is None else ban.numpy(), forbid=fb_host, no_repeat_ngram=n)
+            table = lens = None
+            if width > 0:
+                table = torch.full((bsize, width), tok.pad_token_id, dtype=torch.int32)
+                for i, r in enumerate(rows):
+                    table[i, :len(r)] = torch.as_tensor(r, dtype=torch.int32)
+                lens = torch.as_tensor([len(r) for r in rows], dtype=torch.int32)
+            res = self.engine.decode_constrained(audio, audio_shape[:, 1].to(torch.int32), bos, forbid, w, min_pred, max_pred,
+                                                 prefix=table, prefix_lens=lens, ban_mask=ban, no_repeat_ngram=n, check=False)
+            pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())            # the one host sync
+            mult_preds = res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous()
+            preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()
+            outs = {
+                "cands": self.tokenizer.decode_rec(preds), "preds": preds, "lprobs": res["best_lprobs"],
+                "mult_cands": self.tokenizer.decode_rec(mult_preds), "mult_preds": mult_preds, "mult_lprobs": res["mult_lprobs"],
+                "tasks": tasks,
+            }
+            if clip_probs is not None:
+                outs["tags_probs"] = clip_probs
+                outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
+            return outs
+
     def teacher_forcing(self, x, caps_in: Tensor, sr=None, x_shapes=None, preprocess: bool = True) -> Tensor:
         """CoNeTTEPLM.decode_audio(encode_audio(...), "forcing", caps_in=caps_in) (pl_modules/conette.py:392-417,
         nn/decoding/forcing.py:12-71): logits (B, vocab, cap_len) of given input captions in one causal pass.

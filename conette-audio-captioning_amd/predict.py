@@ -5,6 +5,7 @@
         [--csv_export out.csv] [--precision certified|certified:BASE|bf16|bf16+f16dec|f16|mixed|mixed16|exact|fp32]
         [--sample N --temperature T --top_k K --top_p P --seed S] [--align]
         [--beam_groups G --group_beam W --diversity_penalty L]
+        [--prefix "a dog" --ban_words WORD ... --no_repeat_ngram N]
 
 ``--model_path`` (a Lightning training log directory with hydra/config.yaml + checkpoints/best.ckpt, predict.py:123-178) is
 accepted when the audio encoder's weights come with it: the reference builds its HF wrapper around the Lightning module and leaves
@@ -65,6 +66,12 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
     parser.add_argument("--group_beam", type=int, help="With --beam_groups: beams per group.", default=1)
     parser.add_argument("--diversity_penalty", type=float, default=0.5,
                         help="With --beam_groups: what a candidate pays for each earlier group that picked its token at this step.")
+    parser.add_argument("--prefix", type=_opt_str, default=None,
+                        help="Every caption begins with these words (CoNeTTEModel.caption_constrained): whitespace-separated "
+                             "vocabulary entries.")
+    parser.add_argument("--ban_words", type=str, nargs="+", default=None,
+                        help="Words no caption may hold; words outside the vocabulary are ignored.")
+    parser.add_argument("--no_repeat_ngram", type=int, default=0, help="N > 0: no caption repeats an N-gram.")
     parser.add_argument("--csv_export", type=_opt_str, help="Path to CSV output file.", default=None)
     parser.add_argument("--verbose", type=int, help="Verbose level.", default=1)
     parser.add_argument("--precision", type=str, default=None,
@@ -75,6 +82,10 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
         raise ValueError("--beam_groups searches for different captions; it does not go with --sample")
     if args.beam_groups > 0 and args.align:
         raise ValueError("--align places the words of the searched caption; it does not go with --beam_groups")
+    if args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0:
+        for flag, on in (("--sample", args.sample > 0), ("--beam_groups", args.beam_groups > 0), ("--align", args.align)):
+            if on:
+                raise ValueError(f"--prefix / --ban_words / --no_repeat_ngram steer the beam search; they do not go with {flag}")
     return args
 
 
@@ -197,6 +208,10 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         n = args.beam_groups * args.group_beam
         results = format_results([f for f in fpaths for _ in range(n)], [t for t in outs["tasks"] for _ in range(n)],
                                  [c for cands in outs["mult_cands"] for c in cands])
+    elif args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0:
+        outs = model.caption_constrained(fpaths, prefix=args.prefix, banned=args.ban_words, no_repeat_ngram_size=args.no_repeat_ngram,
+                                         task=tasks)
+        results = format_results(fpaths, outs["tasks"], outs["cands"])
     elif args.sample > 0:   # N draws per file, in the order drawn
         outs = model.sample(fpaths, num_samples=args.sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                             seed=args.seed, task=tasks)

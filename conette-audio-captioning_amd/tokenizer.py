@@ -138,6 +138,22 @@ class AACTokenizer:
     def token_to_id(self, token: str) -> int:
         return self._stoi[token]
 
+    def words_to_ids(self, text: str, skip_unknown: bool = False) -> List[int]:
+        """The ids of the whitespace-separated pieces of ``text`` (lower-cased if the tokenizer lower-cases), each of which must
+        be a vocabulary entry: what ``caption_constrained`` turns a prefix or a list of banned words into.  This is NOT the
+        reference's encoding (spaCy tokenisation + normalisers, training-only and out of scope here): punctuation is not split
+        off and nothing is normalised.  A piece outside the vocabulary raises a ValueError that names it, or is left out with
+        ``skip_unknown``."""
+        if self._hparams.get("lowercase", True):
+            text = text.lower()
+        ids = []
+        for piece in text.split():
+            if piece in self._stoi:
+                ids.append(self._stoi[piece])
+            elif not skip_unknown:
+                raise ValueError(f"{piece!r} is not in the vocabulary")
+        return ids
+
     def add_special_token(self, token: str, count: int = 0) -> int:
         """aac_tokenizer.py:302-316."""
         if token in self._vocab:

@@ -305,6 +305,47 @@ int conette_decode_groups(conette_ctx* ctx, const float* frame_embs, const int32
                           int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes, int32_t* trace_sel, float* trace_val,
                           float* step_logits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Constrained beam search: conette_decode at beam W = `beam` (1..16) whose caller steers the search -- a forced beginning per
+ * clip, tokens that never appear, no n-gram twice -- inside the one search-step launch per decode step (csrc/dec_constrain.h; the
+ * CPU restatement of the rule is conette_amd/constrained_search.py).
+ *   prefix      : dev (B, prefix_width) int32; prefix_lens : dev (B) int32, 0 <= plen[b] <= prefix_width <= max_pred - 1 (values
+ *                 outside are clamped).  With prefix_width == 0 both may be NULL.  The tokens prefix[b][:plen[b]] must lie in
+ *                 [0, vocab) and be neither <eos> nor pad: the caller's contract (a token outside the vocabulary, or <eos>, is
+ *                 treated as a token whose score is not finite, below)
+ *   ban_mask    : dev (vocab) uint8 or NULL;  no_repeat_ngram : n, 0 (off) .. 64
+ * A row's sequence at step i is s_0 (the task token), s_1 .. s_i; a candidate's token becomes s_{i+1}.
+ *   masks on the raw logits z of a candidate row at step i:
+ *     M1  conette_decode's: the EOS floor while i < min_pred, forbid-repeat over s_0 .. s_i
+ *     M2  z[v] = -inf where ban_mask[v] != 0
+ *     M3  (n >= 1) for every j with 0 <= j <= i - n + 1 for which s_j .. s_{j+n-2} equals s_{i-n+2} .. s_i (n - 1 tokens; with
+ *         n = 1 the comparison is empty and always true): z[s_{j+n-1}] = -inf.  Position 0 takes part, as in forbid-repeat
+ *     then lp = (z - max) - log(sum) in fp32, summed in the order of the kernel conette_decode runs at this (vocab, W)
+ *   calls of clip b at step i; model score m = sum_lp[p] + lp[p][v] (i = 0: lp):
+ *     forced   (i < plen[b]) the only candidate is (row 0, t = prefix[b][i]).  m finite: row 0 goes on with t and carries m, the
+ *              clip keeps its W live rows, trace position 0 = (0, t), the others -1, trace_val = m.  m not finite: every one of
+ *              the clip's W slots becomes void and the clip leaves the search
+ *     fan-out  (i == plen[b]) candidates: the V tokens of row 0; k = W picks (plen 0: conette_decode's step 0)
+ *     later    conette_decode's step over the k live rows
+ *     picks    the top k FINITE m, ties to the lowest flat index p * V + v; with only f < k finite candidates there are f picks
+ *              and the slots of row positions f .. k - 1 become void; no index is formed from a pick that does not exist
+ *     void slot  mult_lprobs = -inf, length 0, pad_id throughout; best_* is the first maximum as ever (all slots void:
+ *              best_lprobs = -inf, best_preds all pad)
+ *     bookkeeping  conette_decode's: a finished hypothesis scores m / (i + 1), prefix tokens count in the sum and in the length
+ * The result is the beam search restricted to captions that begin with the prefix; with no mask active its score is what
+ * conette_score gives for the returned caption.  With prefix_width == 0, ban_mask == NULL and n == 0 it is conette_decode, bit for
+ * bit.  Outputs as conette_decode_groups: best / mult / out_sizes, optional trace_sel (max_pred, B, W, 2) / trace_val (max_pred, B, W),
+ * optional step_logits (max_pred, B * W, vocab), RAW; no `margins`, no step0_logits.  The workspace is conette_decode's at beam W.
+ * Asynchronous on `stream`, capturable, never replayed from the decode graph cache; results are bit-identical from run to run.
+ * Works on decoder-only contexts and in every precision. */
+size_t conette_decode_constrained_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t beam,
+                                                  int32_t max_pred);
+int conette_decode_constrained(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                               const uint8_t* forbid_mask, const int32_t* prefix, const int32_t* prefix_lens, int32_t prefix_width,
+                               const uint8_t* ban_mask, int32_t no_repeat_ngram, int32_t batch, int32_t t_audio, int32_t beam,
+                               int32_t min_pred, int32_t max_pred, int32_t* best_preds, float* best_lprobs, int32_t* mult_preds,
+                               float* mult_lprobs, int32_t* out_sizes, int32_t* trace_sel, float* trace_val, float* step_logits,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* a1: torchaudio.functional.resample (preprocessor.py:134-141), sinc_interpolation width 6,
  * rolloff 0.99.  in: dev (rows, n_in) fp32; out: dev (rows, n_out), n_out = ceil(n_in*new/orig). */
 int conette_resample(const float* in, int32_t rows, int32_t n_in, int32_t orig_sr, int32_t new_sr, float* out,
