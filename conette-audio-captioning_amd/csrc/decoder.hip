@@ -11,7 +11,7 @@
 //   * EOS floor, forbid-repeat mask, log-softmax, running sums, per-clip top-k and the
 //     finished / shrinking-k bookkeeping run in one kernel per step with no host sync.
 // This file is the host side: workspace, launch sequences, the hipGraph cache and the entry points.  The device code is in
-// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_constrain.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
+// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_constrain.h, dec_require.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
 #include "ctx.h"
 #include <stdlib.h>
 
@@ -25,6 +25,7 @@
 #include "dec_sample.h"
 #include "dec_group.h"
 #include "dec_constrain.h"
+#include "dec_require.h"
 #include "dec_align.h"
 
 #define FF2_SPLITS 8
@@ -128,6 +129,9 @@ struct DecArgs {
   const int32_t* prefix_lens;
   const uint8_t* ban;
   float* constrain_step_logits;
+  int req_width;               // conette_decode_required: the constrained search with per-clip requirements (dec_require.h); 0: none
+  const int32_t* req_tokens;
+  const int32_t* req_groups;
   bool operator==(const DecArgs& o) const { return memcmp(this, &o, sizeof(DecArgs)) == 0; }
 };
 
@@ -303,6 +307,8 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
   CsArgs cs;  // the constrained search's own arguments
   cs.prefix = a.prefix, cs.prefix_lens = a.prefix_lens, cs.ban = a.ban, cs.step_logits = a.constrain_step_logits;
   cs.P = a.prefix_width, cs.ngram = a.no_repeat_ngram;
+  RqArgs rq;  // the keyword-guided search's own arguments
+  rq.tokens = a.req_tokens, rq.groups = a.req_groups, rq.width = a.req_width;
 
   for (int step = 0; step < maxp; ++step) {
     if (forcing) {
@@ -451,7 +457,8 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
       continue;
     }
     if (a.constrained) {  // the steered step, one launch per step (dec_constrain.h)
-      cn_constrain_step_launch(ss, cs, B, step, s);
+      if (a.req_width > 0) cn_require_step_launch(ss, cs, rq, B, step, s);  // (no table: no requirement, the constrained step)
+      else cn_constrain_step_launch(ss, cs, B, step, s);
       CN_LAUNCH_CHECK();
       continue;
     }
@@ -1052,38 +1059,72 @@ extern "C" size_t conette_decode_constrained_workspace_bytes(const conette_ctx* 
   return conette_decode_workspace_bytes(ctx, batch, t_audio, beam, max_pred);  // (the step keeps nothing of its own between launches)
 }
 
-extern "C" int conette_decode_constrained(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
-                                          const uint8_t* forbid_mask, const int32_t* prefix, const int32_t* prefix_lens,
-                                          int32_t prefix_width, const uint8_t* ban_mask, int32_t no_repeat_ngram, int32_t batch,
-                                          int32_t t_audio, int32_t beam, int32_t min_pred, int32_t max_pred, int32_t* best_preds,
-                                          float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
-                                          int32_t* trace_sel, float* trace_val, float* step_logits, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
+// The checks and the launch of conette_decode_constrained and conette_decode_required (`who`); req_width 0: no requirements.
+static int decode_steered(const char* who, conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                          const uint8_t* forbid_mask, const int32_t* prefix, const int32_t* prefix_lens, int32_t prefix_width,
+                          const uint8_t* ban_mask, int32_t no_repeat_ngram, const int32_t* req_tokens, const int32_t* req_groups,
+                          int32_t req_width, int32_t batch, int32_t t_audio, int32_t beam, int32_t min_pred, int32_t max_pred,
+                          int32_t* best_preds, float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
+                          int32_t* trace_sel, float* trace_val, float* step_logits, void* workspace, size_t workspace_bytes,
+                          void* stream) {
   if (!ctx || !frame_embs || !frame_lens || !bos_ids || !best_preds || !best_lprobs || !mult_preds || !mult_lprobs ||
       !out_sizes || !workspace || batch <= 0 || t_audio <= 0) {
-    cn_set_error("decode_constrained: bad argument");
+    cn_set_error("%s: bad argument", who);
     return CN_ERR_ARG;
   }
   if (beam < 1 || beam > CN_MAX_BEAM) {
-    cn_set_error("decode_constrained: beam=%d unsupported (1..%d)", beam, CN_MAX_BEAM);
+    cn_set_error("%s: beam=%d unsupported (1..%d)", who, beam, CN_MAX_BEAM);
     return CN_ERR_ARG;
   }
-  CN_TRY(dec_check_model(ctx, "decode_constrained", max_pred, min_pred, "decode_constrained: max_pred=%d (1..%d) min_pred=%d unsupported",
-                         max_pred, CN_MAX_PRED, min_pred));
+  CN_TRY(dec_check_model(ctx, who, max_pred, min_pred, "%s: max_pred=%d (1..%d) min_pred=%d unsupported", who, max_pred, CN_MAX_PRED,
+                         min_pred));
   if (prefix_width < 0 || prefix_width > max_pred - 1) {
-    cn_set_error("decode_constrained: prefix_width=%d outside 0 .. max_pred - 1 = %d", prefix_width, max_pred - 1);
+    cn_set_error("%s: prefix_width=%d outside 0 .. max_pred - 1 = %d", who, prefix_width, max_pred - 1);
     return CN_ERR_ARG;
   }
   if (prefix_width > 0 && (!prefix || !prefix_lens)) {
-    cn_set_error("decode_constrained: prefix and prefix_lens must be given with prefix_width=%d > 0", prefix_width);
+    cn_set_error("%s: prefix and prefix_lens must be given with prefix_width=%d > 0", who, prefix_width);
     return CN_ERR_ARG;
   }
   if (no_repeat_ngram < 0 || no_repeat_ngram > CN_MAX_NGRAM) {
-    cn_set_error("decode_constrained: no_repeat_ngram=%d outside 0 .. %d", no_repeat_ngram, CN_MAX_NGRAM);
+    cn_set_error("%s: no_repeat_ngram=%d outside 0 .. %d", who, no_repeat_ngram, CN_MAX_NGRAM);
     return CN_ERR_ARG;
   }
-  CN_TRY(dec_check_workspace("decode_constrained", workspace_bytes,
-                             conette_decode_constrained_workspace_bytes(ctx, batch, t_audio, beam, max_pred)));
+  if (req_width < 0 || req_width > RQ_MAX_TOKENS) {
+    cn_set_error("%s: req_width=%d outside 0 .. %d", who, req_width, RQ_MAX_TOKENS);
+    return CN_ERR_ARG;
+  }
+  if (req_width > 0 && (!req_tokens || !req_groups)) {
+    cn_set_error("%s: req_tokens and req_groups must be given with req_width=%d > 0", who, req_width);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_workspace(who, workspace_bytes, conette_decode_workspace_bytes(ctx, batch, t_audio, beam, max_pred)));
+  if (req_width > 0) {  // the group indices, read back unless the stream is capturing (then a bad entry counts as unused)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    CN_HIP(hipStreamIsCapturing((hipStream_t)stream, &cap));
+    if (cap == hipStreamCaptureStatusNone) {
+      const size_t n = (size_t)batch * req_width;
+      int32_t* host = (int32_t*)malloc(n * sizeof(int32_t));
+      if (!host) {
+        cn_set_error("%s: out of host memory", who);
+        return CN_ERR_ARG;
+      }
+      hipError_t e = hipMemcpyAsync(host, req_groups, n * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+      if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+      size_t bad = n;
+      if (e == hipSuccess)
+        for (size_t i = 0; i < n && bad == n; ++i)
+          if (host[i] < -1 || host[i] >= RQ_MAX_GROUPS) bad = i;
+      const int32_t bad_value = bad < n ? host[bad] : 0;
+      free(host);
+      CN_HIP(e);
+      if (bad < n) {
+        cn_set_error("%s: req_groups[%d][%d]=%d outside -1 .. %d", who, (int)(bad / req_width), (int)(bad % req_width), bad_value,
+                     RQ_MAX_GROUPS - 1);
+        return CN_ERR_ARG;
+      }
+    }
+  }
   DecArgs a;
   memset(&a, 0, sizeof(a));
   a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.bos_ids = bos_ids, a.forbid = forbid_mask, a.ws = (char*)workspace;
@@ -1093,8 +1134,40 @@ extern "C" int conette_decode_constrained(conette_ctx* ctx, const float* frame_e
   a.constrained = 1, a.prefix_width = prefix_width, a.no_repeat_ngram = no_repeat_ngram;
   if (prefix_width > 0) a.prefix = prefix, a.prefix_lens = prefix_lens;
   a.ban = ban_mask, a.constrain_step_logits = step_logits;
+  if (req_width > 0) a.req_width = req_width, a.req_tokens = req_tokens, a.req_groups = req_groups;
   // (eager, as conette_sample: the launch sequence is static and holds no host state, so the caller may capture it)
   CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, (hipStream_t)stream));
+}
+
+extern "C" int conette_decode_constrained(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                                          const uint8_t* forbid_mask, const int32_t* prefix, const int32_t* prefix_lens,
+                                          int32_t prefix_width, const uint8_t* ban_mask, int32_t no_repeat_ngram, int32_t batch,
+                                          int32_t t_audio, int32_t beam, int32_t min_pred, int32_t max_pred, int32_t* best_preds,
+                                          float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
+                                          int32_t* trace_sel, float* trace_val, float* step_logits, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  return decode_steered("decode_constrained", ctx, frame_embs, frame_lens, bos_ids, forbid_mask, prefix, prefix_lens, prefix_width,
+                        ban_mask, no_repeat_ngram, nullptr, nullptr, 0, batch, t_audio, beam, min_pred, max_pred, best_preds, best_lprobs,
+                        mult_preds, mult_lprobs, out_sizes, trace_sel, trace_val, step_logits, workspace, workspace_bytes, stream);
+}
+
+// ---- keyword-guided beam search (dec_require.h): the constrained search with per-clip requirements ----
+extern "C" size_t conette_decode_required_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t beam,
+                                                          int32_t max_pred) {
+  return conette_decode_constrained_workspace_bytes(ctx, batch, t_audio, beam, max_pred);  // (a row's requirement state is its sequence)
+}
+
+extern "C" int conette_decode_required(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                                       const uint8_t* forbid_mask, const int32_t* prefix, const int32_t* prefix_lens,
+                                       int32_t prefix_width, const uint8_t* ban_mask, int32_t no_repeat_ngram, const int32_t* req_tokens,
+                                       const int32_t* req_groups, int32_t req_width, int32_t batch, int32_t t_audio, int32_t beam,
+                                       int32_t min_pred, int32_t max_pred, int32_t* best_preds, float* best_lprobs, int32_t* mult_preds,
+                                       float* mult_lprobs, int32_t* out_sizes, int32_t* trace_sel, float* trace_val, float* step_logits,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_steered("decode_required", ctx, frame_embs, frame_lens, bos_ids, forbid_mask, prefix, prefix_lens, prefix_width, ban_mask,
+                        no_repeat_ngram, req_tokens, req_groups, req_width, batch, t_audio, beam, min_pred, max_pred, best_preds,
+                        best_lprobs, mult_preds, mult_lprobs, out_sizes, trace_sel, trace_val, step_logits, workspace, workspace_bytes,
+                        stream);
 }
 
 extern "C" size_t conette_greedy_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t max_pred) {

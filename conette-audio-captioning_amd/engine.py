@@ -35,6 +35,7 @@ EXPORTS = (
     "conette_score_workspace_bytes", "conette_score", "conette_sample_workspace_bytes", "conette_sample",
     "conette_align_workspace_bytes", "conette_align", "conette_decode_groups_workspace_bytes", "conette_decode_groups",
     "conette_decode_constrained_workspace_bytes", "conette_decode_constrained",
+    "conette_decode_required_workspace_bytes", "conette_decode_required",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -168,6 +169,13 @@ def load_library() -> C.CDLL:
                                                C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_decode_required_workspace_bytes.restype = C.c_size_t
+    lib.conette_decode_required_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_decode_required.restype = C.c_int
+    lib.conette_decode_required.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.conette_greedy_workspace_bytes.restype = C.c_size_t
     lib.conette_greedy_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.conette_greedy.restype = C.c_int
@@ -827,17 +835,49 @@ class Engine:
         [, "step_logits" (max_pred, B * beam, vocab), the raw logits each step decided on].  ``check``: the prefix tokens are
         checked on the host (in the vocabulary, neither <eos> nor pad; a device prefix is copied back for it); ``exact``
         (certified engines only): run on the exact context."""
-        from . import constrained_search
+        return self._decode_steered("decode_constrained", frame_embs, frame_lens, bos_ids, forbid_mask, beam, min_pred, max_pred, prefix,
+                                    prefix_lens, ban_mask, no_repeat_ngram, None, None, want_trace, want_logits, exact, check)
+
+    def decode_required(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, bos_ids: torch.Tensor,
+                        forbid_mask: Optional[torch.Tensor], beam: int, min_pred: int, max_pred: int,
+                        prefix: Optional[torch.Tensor] = None, prefix_lens: Optional[torch.Tensor] = None,
+                        ban_mask: Optional[torch.Tensor] = None, no_repeat_ngram: int = 0, req_tokens: Optional[torch.Tensor] = None,
+                        req_groups: Optional[torch.Tensor] = None, want_trace: bool = False, want_logits: bool = False,
+                        exact: bool = False, check: bool = True) -> Dict[str, torch.Tensor]:
+        """Keyword-guided beam search (conette_decode_required, include/conette_hip.h; the rule: required_search.py):
+        ``decode_constrained`` whose every caption holds a token of each of a clip's requirement groups.  ``req_tokens`` /
+        ``req_groups`` (B, width <= 32) int: the clip's required tokens and the group 0 .. 7 of each, -1 = unused entry
+        (``required_search.pack_tables``); both None: no requirement.  Outputs and switches as ``decode_constrained``; ``check``
+        also holds the tables to ``required_search.check_requirements`` on the host."""
+        if (req_tokens is None) != (req_groups is None):
+            raise ValueError("req_tokens and req_groups must be given together")
+        if req_tokens is None:
+            req_tokens = req_groups = torch.zeros((frame_embs.shape[0], 0), dtype=torch.int32)
+        return self._decode_steered("decode_required", frame_embs, frame_lens, bos_ids, forbid_mask, beam, min_pred, max_pred, prefix,
+                                    prefix_lens, ban_mask, no_repeat_ngram, req_tokens, req_groups, want_trace, want_logits, exact, check)
+
+    def _decode_steered(self, entry, frame_embs, frame_lens, bos_ids, forbid_mask, beam, min_pred, max_pred, prefix, prefix_lens,
+                        ban_mask, no_repeat_ngram, req_tokens, req_groups, want_trace, want_logits, exact, check):
+        """decode_constrained (``req_tokens`` None) and decode_required: one preparation, the entry ``conette_<entry>``"""
+        from . import constrained_search, required_search
         b, t, _ = frame_embs.shape
         max_pred = int(max_pred)
         pw = 0 if prefix is None else int(prefix.shape[1])
         if prefix is not None and (prefix.dim() != 2 or prefix.shape[0] != b):
             raise ValueError(f"prefix must be (batch, P), got {tuple(prefix.shape)}")
-        w, n = constrained_search.check_arguments(beam, no_repeat_ngram, max_pred, pw)
+        rw = 0
+        if req_tokens is not None:
+            if req_tokens.dim() != 2 or req_tokens.shape[0] != b or tuple(req_groups.shape) != tuple(req_tokens.shape):
+                raise ValueError(f"req_tokens and req_groups must both be (batch, width), got {tuple(req_tokens.shape)} and "
+                                 f"{tuple(req_groups.shape)}")
+            rw = int(req_tokens.shape[1])
+            w, n = required_search.check_arguments(beam, no_repeat_ngram, max_pred, pw, rw)
+        else:
+            w, n = constrained_search.check_arguments(beam, no_repeat_ngram, max_pred, pw)
         ctx = self._ctx_dec
         if exact:
             if self._ctx_x is None:
-                raise RuntimeError("decode_constrained(exact=True) needs a certified engine")
+                raise RuntimeError(f"{entry}(exact=True) needs a certified engine")
             ctx = self._ctx_x
         pre = plens = None
         if pw > 0:
@@ -870,14 +910,44 @@ class Engine:
              "trace_sel": e((max_pred, b, w, 2), torch.int32) if want_trace else None,
              "trace_val": e((max_pred, b, w), torch.float32) if want_trace else None,
              "step_logits": e((max_pred, b * w, self.vocab_size), torch.float32) if want_logits else None}
-        need = self.lib.conette_decode_constrained_workspace_bytes(ctx, b, t, w, max_pred)
-        wsb = self._workspace("xdec" if exact else "dec", need)
-        st = self.lib.conette_decode_constrained(ctx, _ptr(fe), _ptr(lens_in), _ptr(bos), _ptr(fm), _ptr(pre), _ptr(plens), pw, _ptr(bm),
-                                                 n, b, t, w, int(min_pred), max_pred, _ptr(o["best_preds"]), _ptr(o["best_lprobs"]),
-                                                 _ptr(o["mult_preds"]), _ptr(o["mult_lprobs"]), _ptr(o["sizes"]), _ptr(o["trace_sel"]),
-                                                 _ptr(o["trace_val"]), _ptr(o["step_logits"]), _ptr(wsb), wsb.numel(), _stream())
-        _check(st, "conette_decode_constrained")
+        outs = (_ptr(o["best_preds"]), _ptr(o["best_lprobs"]), _ptr(o["mult_preds"]), _ptr(o["mult_lprobs"]), _ptr(o["sizes"]),
+                _ptr(o["trace_sel"]), _ptr(o["trace_val"]), _ptr(o["step_logits"]))
+        if req_tokens is None:
+            need = self.lib.conette_decode_constrained_workspace_bytes(ctx, b, t, w, max_pred)
+            wsb = self._workspace("xdec" if exact else "dec", need)
+            st = self.lib.conette_decode_constrained(ctx, _ptr(fe), _ptr(lens_in), _ptr(bos), _ptr(fm), _ptr(pre), _ptr(plens), pw, _ptr(bm),
+                                                     n, b, t, w, int(min_pred), max_pred, *outs, _ptr(wsb), wsb.numel(), _stream())
+        else:
+            rt = rg = None
+            if rw > 0:
+                if check:
+                    self._check_req_tables(req_tokens, req_groups, bos_ids, prefix, prefix_lens, ban_mask, max_pred)
+                rt = req_tokens.to(self.device, torch.int32).contiguous()
+                rg = req_groups.to(self.device, torch.int32).contiguous()
+            need = self.lib.conette_decode_required_workspace_bytes(ctx, b, t, w, max_pred)
+            wsb = self._workspace("xdec" if exact else "dec", need)
+            st = self.lib.conette_decode_required(ctx, _ptr(fe), _ptr(lens_in), _ptr(bos), _ptr(fm), _ptr(pre), _ptr(plens), pw, _ptr(bm),
+                                                  n, _ptr(rt), _ptr(rg), rw, b, t, w, int(min_pred), max_pred, *outs, _ptr(wsb),
+                                                  wsb.numel(), _stream())
+        _check(st, "conette_" + entry)
         return {k: v for k, v in o.items() if v is not None}
+
+    def _check_req_tables(self, req_tokens, req_groups, bos_ids, prefix, prefix_lens, ban_mask, max_pred) -> None:
+        """the host check of decode_required: every clip's table against required_search.check_requirements"""
+        from . import required_search
+        th, gh, bos = req_tokens.cpu().long(), req_groups.cpu().long(), bos_ids.cpu().long()
+        if bool(((gh < -1) | (gh >= required_search.MAX_GROUPS)).any()):
+            raise ValueError(f"req_groups must lie in -1 .. {required_search.MAX_GROUPS - 1}")
+        ban = None if ban_mask is None else ban_mask.cpu().bool().numpy()
+        for i in range(th.shape[0]):
+            used = sorted(set(gh[i][gh[i] >= 0].tolist()))
+            groups = [[int(x) for x in th[i][gh[i] == g].tolist()] for g in used]
+            pre = []
+            if prefix is not None:
+                n_pre = int(prefix.shape[1]) if prefix_lens is None else int(prefix_lens.reshape(-1)[i])
+                pre = [int(x) for x in prefix[i, :n_pre].cpu().tolist()]
+            required_search.check_requirements(groups, int(bos[i]), vocab_size=self.vocab_size, max_pred=max_pred, eos_id=self.eos_id,
+                                               pad_id=self.pad_id, ban=ban, prefix=pre)
 
     def decode_input_buffer(self, b: int, t: int, beam: int, max_pred: int, slot: int = 0, margins: bool = False,
                             exact: bool = False) -> torch.Tensor:

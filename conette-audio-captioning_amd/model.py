@@ -58,6 +58,49 @@ def probs_to_names(probs: Tensor, threshold: Union[float, Tensor], idx_to_name: 
     return [[idx_to_name[int(j)] for j in torch.where(row)[0].tolist()] for row in mask]
 
 
+def _requirement_groups(tok, spec) -> List[List[int]]:
+    """One clip's requirement groups from a spec: a string (split on whitespace, each word its own group) or a list whose items
+    are a word, an id, or a list of alternatives.  An unknown alternative is dropped while its group keeps a known one; a group
+    left empty is a ValueError that names its words."""
+    if isinstance(spec, str):
+        items = spec.split()
+    elif isinstance(spec, (list, tuple)):
+        items = list(spec)
+    else:
+        raise ValueError(f"a requirement spec is a string or a list of words, ids or lists of alternatives, not {type(spec).__name__}")
+    groups = []
+    for item in items:
+        alts = list(item) if isinstance(item, (list, tuple)) else [item]
+        ids: List[int] = []
+        for a in alts:
+            if isinstance(a, str):
+                found = tok.words_to_ids(a, skip_unknown=True)
+                if len(a.split()) != 1:
+                    raise ValueError(f"required word {a!r}: a requirement is one word (phrases are not supported)")
+                ids += found
+            elif isinstance(a, bool) or not isinstance(a, int):
+                raise ValueError(f"a required alternative is a word or an id, not {a!r}")
+            else:
+                ids.append(int(a))
+        if not ids:
+            raise ValueError("required word " + " | ".join(repr(a) for a in alts) + " is not in the vocabulary")
+        groups.append(list(dict.fromkeys(ids)))
+    return groups
+
+
+def required_groups(tok, required, required_per_clip, bsize: int) -> List[List[List[int]]]:
+    """Per clip the requirement groups of ``CoNeTTEModel.caption_constrained``'s ``required`` (one spec for all clips) or
+    ``required_per_clip`` (a list of ``bsize`` specs, None = none for that clip); ``tok`` needs ``words_to_ids`` only."""
+    if required is not None and required_per_clip is not None:
+        raise ValueError("required and required_per_clip exclude each other")
+    if required_per_clip is not None:
+        if isinstance(required_per_clip, str) or len(required_per_clip) != bsize:
+            raise ValueError(f"required_per_clip must be a list of {bsize} specs, one per clip")
+        return [[] if s is None else _requirement_groups(tok, s) for s in required_per_clip]
+    one = [] if required is None else _requirement_groups(tok, required)
+    return [[list(g) for g in one] for _ in range(bsize)]
+
+
 def _read_state_dict(path: str) -> Dict[str, Tensor]:
     st = osp.join(path, "model.safetensors")
     if osp.isfile(st):
@@ -460,6 +503,10 @@ class CoNeTTEModel:
                 outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
             return outs
 
+    def required_groups(self, required, required_per_clip, bsize: int) -> List[List[List[int]]]:
+        """per clip the requirement groups (token lists) of ``caption_constrained``'s ``required`` / ``required_per_clip``"""
+        return required_groups(self.tokenizer, required, required_per_clip, bsize)
+
     def _prefix_rows(self, prefix, bsize: int) -> List[List[int]]:
         """one token list per clip from ``caption_constrained``'s ``prefix``: None, one string, one string per clip, or padded ids"""
         if prefix is None:
@@ -486,7 +533,8 @@ class CoNeTTEModel:
     def caption_constrained(self, x, prefix=None, banned=None, no_repeat_ngram_size: int = 0, beam_size: Optional[int] = None, sr=None,
                             x_shapes=None, preprocess: bool = True, task: Union[str, List[str], None] = None,
                             min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
-                            forbid_rep_mode: Optional[str] = None, threshold: Union[float, Tensor] = 0.3) -> Dict[str, Any]:
+                            forbid_rep_mode: Optional[str] = None, threshold: Union[float, Tensor] = 0.3, *, required=None,
+                            required_per_clip=None) -> Dict[str, Any]:
         """The beam search of ``forward``, steered on the device (conette_decode_constrained; the rule: constrained_search.py):
         every caption begins with ``prefix`` -- one string for all clips, one string per clip, or ids (B, P) right-padded with
         pad_id --, never holds a token of ``banned`` (words or ids) and repeats no ``no_repeat_ngram_size``-gram (0: off; the task
@@ -497,8 +545,18 @@ class CoNeTTEModel:
         ban of <eos>.  Returns ``forward``'s keys; scores are the model's mean log-probabilities, prefix tokens included; a
         hypothesis slot the constraints left empty has ``mult_lprobs`` -inf and an empty caption.  Precision "certified*" and
         the mixed precisions run this search on the base pipeline's decoder context, with no exact re-run: no certificate is
-        defined for it.  With waveforms in, an overflow of the 16-bit encoders' fp16 residual stream raises as in ``sample``."""
+        defined for it.  With waveforms in, an overflow of the 16-bit encoders' fp16 residual stream raises as in ``sample``.
+
+        ``required`` (for all clips) or ``required_per_clip`` (a list of one spec per clip; the two exclude each other): words
+        every caption must hold (conette_decode_required; the rule: required_search.py).  A spec is a string -- split on
+        whitespace, each word its own requirement -- or a list whose items are a word, an id, or a list of alternatives ("dog" or
+        "dogs"); at most 8 requirements and 32 tokens per clip.  An unknown alternative is dropped while its group keeps a known
+        one; a group left empty is a ValueError that names the word, as is a required word that is banned, special, in two groups,
+        or more requirements than ``max_pred_size`` leaves room for after the prefix.  Every caption that is returned non-empty
+        then holds a word of every group, and none ends before it does.  With both None the call is what it was."""
         from . import constrained_search
+        if required is not None and required_per_clip is not None:
+            raise ValueError("required and required_per_clip exclude each other")
         with torch.cuda.device(self.device):
             keep: dict = {}
             audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess, keep)
@@ -544,8 +602,22 @@ class CoNeTTEModel:
                 for i, r in enumerate(rows):
                     table[i, :len(r)] = torch.as_tensor(r, dtype=torch.int32)
                 lens = torch.as_tensor([len(r) for r in rows], dtype=torch.int32)
-            res = self.engine.decode_constrained(audio, audio_shape[:, 1].to(torch.int32), bos, forbid, w, min_pred, max_pred,
-                                                 prefix=table, prefix_lens=lens, ban_mask=ban, no_repeat_ngram=n, check=False)
+            if required is None and required_per_clip is None:
+                res = self.engine.decode_constrained(audio, audio_shape[:, 1].to(torch.int32), bos, forbid, w, min_pred, max_pred,
+                                                     prefix=table, prefix_lens=lens, ban_mask=ban, no_repeat_ngram=n, check=False)
+            else:
+                from . import required_search
+                groups = required_groups(tok, required, required_per_clip, bsize)
+                names = {t: tok.id_to_token(t) for r in groups for g in r for t in g if 0 <= t < min(vocab, tok.get_vocab_size())}
+                groups = [required_search.check_requirements(g, int(t), vocab_size=vocab, max_pred=max_pred, eos_id=tok.eos_token_id,
+                                                             pad_id=tok.pad_token_id, bos_id=tok.bos_token_id,
+                                                             ban=None if ban is None else ban.numpy(), prefix=r, words=names)
+                          for g, r, t in zip(groups, rows, bos.tolist())]
+                rt, rg = required_search.pack_tables(groups)
+                required_search.check_arguments(w, n, max_pred, width, rt.shape[1])
+                res = self.engine.decode_required(audio, audio_shape[:, 1].to(torch.int32), bos, forbid, w, min_pred, max_pred,
+                                                  prefix=table, prefix_lens=lens, ban_mask=ban, no_repeat_ngram=n,
+                                                  req_tokens=torch.from_numpy(rt), req_groups=torch.from_numpy(rg), check=False)
             pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())            # the one host sync
             mult_preds = res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous()
             preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()

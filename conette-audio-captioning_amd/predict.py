@@ -72,6 +72,9 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
     parser.add_argument("--ban_words", type=str, nargs="+", default=None,
                         help="Words no caption may hold; words outside the vocabulary are ignored.")
     parser.add_argument("--no_repeat_ngram", type=int, default=0, help="N > 0: no caption repeats an N-gram.")
+    parser.add_argument("--require_words", type=str, nargs="+", default=None,
+                        help="Words every caption must hold (CoNeTTEModel.caption_constrained(required=...)); 'bark|barks' asks for "
+                             "one of the alternatives.")
     parser.add_argument("--csv_export", type=_opt_str, help="Path to CSV output file.", default=None)
     parser.add_argument("--verbose", type=int, help="Verbose level.", default=1)
     parser.add_argument("--precision", type=str, default=None,
@@ -82,10 +85,10 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
         raise ValueError("--beam_groups searches for different captions; it does not go with --sample")
     if args.beam_groups > 0 and args.align:
         raise ValueError("--align places the words of the searched caption; it does not go with --beam_groups")
-    if args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0:
+    if args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0 or args.require_words is not None:
         for flag, on in (("--sample", args.sample > 0), ("--beam_groups", args.beam_groups > 0), ("--align", args.align)):
             if on:
-                raise ValueError(f"--prefix / --ban_words / --no_repeat_ngram steer the beam search; they do not go with {flag}")
+                raise ValueError(f"--prefix / --ban_words / --no_repeat_ngram / --require_words steer the beam search; they do not go with {flag}")
     return args
 
 
@@ -208,9 +211,10 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         n = args.beam_groups * args.group_beam
         results = format_results([f for f in fpaths for _ in range(n)], [t for t in outs["tasks"] for _ in range(n)],
                                  [c for cands in outs["mult_cands"] for c in cands])
-    elif args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0:
+    elif args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0 or args.require_words is not None:
+        required = None if args.require_words is None else [w.split("|") for w in args.require_words]
         outs = model.caption_constrained(fpaths, prefix=args.prefix, banned=args.ban_words, no_repeat_ngram_size=args.no_repeat_ngram,
-                                         task=tasks)
+                                         task=tasks, required=required)
         results = format_results(fpaths, outs["tasks"], outs["cands"])
     elif args.sample > 0:   # N draws per file, in the order drawn
         outs = model.sample(fpaths, num_samples=args.sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,

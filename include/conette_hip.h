@@ -346,6 +346,42 @@ int conette_decode_constrained(conette_ctx* ctx, const float* frame_embs, const 
                                float* mult_lprobs, int32_t* out_sizes, int32_t* trace_sel, float* trace_val, float* step_logits,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Keyword-guided beam search: conette_decode_constrained whose every caption must hold a token of each of a clip's G <= 8
+ * requirement groups (dynamic beam allocation) -- inside the same one search-step launch per decode step (csrc/dec_require.h; the
+ * CPU restatement of the rule is conette_amd/required_search.py).  Arguments and outputs are conette_decode_constrained's, plus
+ *   req_tokens  : dev (B, req_width) int32, the clip's required tokens;  req_groups : dev (B, req_width) int32, the group 0 .. 7 of
+ *                 each, -1 = unused entry (any order, gaps allowed).  0 <= req_width <= 32; with req_width == 0 both may be NULL.
+ *                 The caller's contract: no token in two groups of a clip, none is <eos>, pad, <bos>, the clip's task token or a
+ *                 banned token, and the groups the prefix leaves unmet number at most max_pred - plen[b].  A group index outside
+ *                 -1 .. 7 is an argument error: the table is read back for that check, so the call waits for `stream` (not while
+ *                 the stream is capturing: there such an entry, like a token outside the vocabulary or one an earlier entry of the
+ *                 clip holds, counts as unused)
+ * Group g of a row is MET when one of its tokens occurs among s_1 .. s_i (prefix tokens count); unmet(p) = unmet groups of row p,
+ * c(p) = G - unmet(p).  A row's state is derived from its own sequence: the search carries nothing new.
+ *   masks, after M1 .. M3, on every call of a row, forced calls included:
+ *     M4  while unmet(p) > 0: z[eos] = -inf
+ *     M5  if unmet(p) >= max_pred - i: z[v] = -inf for every v that is no token of one of the row's unmet groups
+ *   banks    candidate (p, v) is in bank c(p) + 1 if v belongs to an unmet group of row p, else in bank c(p)
+ *   picks of a free call with k slots: per bank the candidates are ordered by descending finite m, ties to the lowest flat index
+ *            p * V + v; the slots are dealt round-robin from the highest non-empty bank to the lowest, again and again, skipping
+ *            exhausted banks, until k picks or until no finite candidate is left.  Pick order is deal order (trace_sel / trace_val,
+ *            and which row goes on in which position).  Fewer finite candidates than k: void slots, as conette_decode_constrained
+ *   forced calls are conette_decode_constrained's, under M4 / M5
+ * Under the caller's contract every hypothesis that is not void holds a token of every group and ends in <eos> or at max_pred; M5
+ * can leave a call fewer finite candidates than slots (a fan-out with fewer unmet-group tokens than W), which gives void slots, never
+ * an indexed non-pick.  With req_width == 0, and
+ * for every clip without a used entry, the result is conette_decode_constrained's, bit for bit.  The workspace is
+ * conette_decode's at beam W.  Capturable, never replayed from the decode graph cache; results are bit-identical from run to run.
+ * Works on decoder-only contexts and in every precision. */
+size_t conette_decode_required_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t beam, int32_t max_pred);
+int conette_decode_required(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, const int32_t* bos_ids,
+                            const uint8_t* forbid_mask, const int32_t* prefix, const int32_t* prefix_lens, int32_t prefix_width,
+                            const uint8_t* ban_mask, int32_t no_repeat_ngram, const int32_t* req_tokens, const int32_t* req_groups,
+                            int32_t req_width, int32_t batch, int32_t t_audio, int32_t beam, int32_t min_pred, int32_t max_pred,
+                            int32_t* best_preds, float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
+                            int32_t* trace_sel, float* trace_val, float* step_logits, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 /* a1: torchaudio.functional.resample (preprocessor.py:134-141), sinc_interpolation width 6,
  * rolloff 0.99.  in: dev (rows, n_in) fp32; out: dev (rows, n_out), n_out = ceil(n_in*new/orig). */
 int conette_resample(const float* in, int32_t rows, int32_t n_in, int32_t orig_sr, int32_t new_sr, float* out,
