@@ -12,6 +12,8 @@ def __getattr__(name):  # lazy: importing the package must not need a GPU or the
     import importlib
     if name == "CoNeTTEModel":
         return importlib.import_module(__name__ + ".model").CoNeTTEModel
+    if name == "CoNeTTEEnsemble":   # several checkpoints, one search (ensemble.py)
+        return importlib.import_module(__name__ + ".ensemble").CoNeTTEEnsemble
     if name == "Engine":
         return importlib.import_module(__name__ + ".engine").Engine
     if name == "BaselinePLM":   # the reference's second checkpoint family (pl_modules/baseline.py): no task tokens, no audio encoder

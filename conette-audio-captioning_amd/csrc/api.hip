@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <atomic>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -273,6 +274,8 @@ extern "C" int conette_create(const conette_config* cfg, int32_t n_tensors, cons
   conette_ctx* ctx = new conette_ctx();
   memset(ctx, 0, sizeof(*ctx));
   ctx->cfg = *cfg;
+  static std::atomic<unsigned long long> next_serial{0};
+  ctx->serial = ++next_serial;
   ctx->rt = new CnRuntime();
   ctx->esize = (cfg->precision == CONETTE_PREC_BF16 || cfg->precision == CONETTE_PREC_F16) ? 2 : 4;
   ctx->f16 = cfg->precision == CONETTE_PREC_F16 ? 1 : 0;

@@ -71,6 +71,7 @@ struct conette_ctx {
   conette_config cfg;
   CnRuntime* rt;
   void* dec_graphs;  // DecGraphCache of decoder.hip (hipGraph replay of conette_decode), owned by the context
+  unsigned long long serial;  // process-unique, never reused (conette_create): part of a graph key that names ANOTHER context (decoder.hip)
   uint32_t prof_mask;
   int dec_unfused;  // CONETTE_OPT_DECODE_FUSION = 0: one launch per sub-layer (the cross-check path of the tests)
   int esize;  // operand element size (2 or 4)

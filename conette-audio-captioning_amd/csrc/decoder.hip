@@ -11,7 +11,7 @@
 //   * EOS floor, forbid-repeat mask, log-softmax, running sums, per-clip top-k and the
 //     finished / shrinking-k bookkeeping run in one kernel per step with no host sync.
 // This file is the host side: workspace, launch sequences, the hipGraph cache and the entry points.  The device code is in
-// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_constrain.h, dec_require.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
+// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_constrain.h, dec_require.h, dec_ensemble.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
 #include "ctx.h"
 #include <stdlib.h>
 
@@ -27,6 +27,7 @@
 #include "dec_constrain.h"
 #include "dec_require.h"
 #include "dec_align.h"
+#include "dec_ensemble.h"
 
 #define FF2_SPLITS 8
 static int ff2_splits_default() { return 4; }  // split-K slabs of the unfused FFN2 GEMM at small R
@@ -132,6 +133,22 @@ struct DecArgs {
   int req_width;               // conette_decode_required: the constrained search with per-clip requirements (dec_require.h); 0: none
   const int32_t* req_tokens;
   const int32_t* req_groups;
+  // conette_decode_ensemble (dec_ensemble.h): every member, member 0 included (whose context runs the graph cache).  INVARIANT: a
+  // key with n_members > 0 names other contexts' weights, which a cached graph's launches read.  A pointer alone does not identify
+  // a context -- a later conette_create may be handed the address of a destroyed one -- so the key also holds every member's
+  // process-unique serial number (conette_ctx::serial, never reused): a recycled address gives another key, and the stale graph,
+  // whose launches would read freed weights, is never replayed (it ages out of the cache like any other entry).
+  int n_members, combine;
+  conette_ctx* ens_ctx[CN_MAX_MEMBERS];
+  unsigned long long ens_serial[CN_MAX_MEMBERS];
+  const float* ens_fe[CN_MAX_MEMBERS];
+  const int32_t* ens_bos[CN_MAX_MEMBERS];
+  char* ens_ws[CN_MAX_MEMBERS];
+  float ens_w[CN_MAX_MEMBERS];
+  // a member's launch sequence depends on its CONETTE_OPT_DECODE_FUSION, and only the context whose option changes flushes its
+  // own cache: the flag of every member is part of the key, so a graph with the other sequence is never replayed
+  int ens_unfused[CN_MAX_MEMBERS];
+  float* ens_step_logits;  // optional
   bool operator==(const DecArgs& o) const { return memcmp(this, &o, sizeof(DecArgs)) == 0; }
 };
 
@@ -254,21 +271,134 @@ static int dec_sublayer_layer(conette_ctx* ctx, const DecWs& w, int l, const int
   return CN_OK;
 }
 
+// ---- one decode step's forward, embedding through classifier: the R rows' tokens `tok` at position `step` -> w.logits ----------
+// The activations, the KV cache and the cross K/V are those of `w`; the search state the kernels read is passed beside it -- `tok`
+// (R) the rows' current tokens, `anc` (R, maxp) their ancestor table, `gate` (null: none) the count of rows still searching --
+// so that the members of an ensemble run on the state of member 0 (decode_ensemble_impl) while every other caller passes its own.
 template <typename T>
-static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
+static int dec_step_forward(conette_ctx* ctx, const DecWs& w, const int* tok, int* anc, const int* gate, const unsigned long long* kvalid,
+                            const int32_t* frame_lens, int B, int Ta, int beam, int maxp, int step, int db_debug, hipStream_t s) {
   const conette_config& cfg = ctx->cfg;
-  const int B = a.B, Ta = a.Ta, beam = a.beam, min_pred = a.min_pred, maxp = a.maxp;
   const int d = cfg.d_model, NL = cfg.n_layers, R = B * beam, V = cfg.vocab_size, dff = cfg.d_ff;
-  DecWs w = dec_ws(ctx, B, Ta, beam, maxp, a.ws);
-  const bool forcing = a.force_caps != nullptr;
-  const bool sampling = a.uniforms != nullptr;
-  const unsigned long long* kvalid = forcing ? w.kvalid : nullptr;
   T* kvc = (T*)w.kvc;
   T* xt = (T*)w.xt;
   T* ffh = (T*)w.ffh;
   const int kv_ld = NL * 2 * d;
   const float scale = 1.0f / sqrtf((float)(d / cfg.nhead));
   const int rblocks = cn_cdiv(R, 4);
+  // fused path (dec_block.h + dec_ffn.h): 16-bit operands, and since round 4 the exact precision (hi / lo passes of the same
+  // two kernels; needs both packed streams, i.e. d_ff % 256 == 0 and d_ff <= 2048)
+  constexpr bool kBlockT = CnIsH16<T>::value || std::is_same<T, sp16_t>::value;
+  const bool block_path = kBlockT && !ctx->dec_unfused && ctx->layers[0].blk_w != nullptr &&
+                          (CnIsH16<T>::value || (ctx->layers[0].ffn_w != nullptr && dff / 256 <= FF2_SPLITS));
+  if (!block_path) {  // (the block path embeds in the prologue of layer 0's block kernel)
+    hipLaunchKernelGGL((cn_embed_kernel<T>), dim3(rblocks), dim3(256), 0, s, tok, ctx->emb, ctx->pe, step, 0, R,
+                       sqrtf((float)d), w.x, xt);
+    CN_LAUNCH_CHECK();
+  }
+  bool fused_done = false;
+  if constexpr (kBlockT) if (block_path) {
+    // default path: 3 launches per layer -- fused block (embedding | previous LN3, QKV, self-attention,
+    // cross-attention: dec_block.h), FFN1 GEMM + GELU, FFN2 split-K slabs (summed by the next layer's block
+    // prologue; the last layer's by the LN3 kernel in front of the classifier)
+    fused_done = true;
+    int splits = ff2_splits_default();
+    if (splits < 1 || splits > FF2_SPLITS || splits > 8 || dff % (splits * 64) != 0) splits = 1;
+    // fused FFN (dec_ffn.h): one launch per layer, one slab per 256-wide hidden chunk
+    const bool ffn_fused = ctx->layers[0].ffn_w != nullptr && dff / 256 <= FF2_SPLITS;
+    if (ffn_fused) splits = dff / 256;
+    const size_t slab = (size_t)R * d;
+    for (int l = 0; l < NL; ++l) {
+      const CnLayerW& lw = ctx->layers[l];
+      T* kc = (T*)w.kc + (size_t)l * maxp * R * d;
+      T* vc = (T*)w.vc + (size_t)l * maxp * R * d;
+      {
+        CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
+        DbPrologue pro;
+        pro.tok = tok, pro.emb = ctx->emb, pro.pe_row = ctx->pe + (size_t)step * d, pro.emb_scale = sqrtf((float)d);
+        pro.slabs = nullptr, pro.nslab = 0, pro.slab_stride = slab, pro.b2_prev = nullptr, pro.g3 = nullptr, pro.b3 = nullptr;
+        if (l > 0) {
+          const CnLayerW& pw = ctx->layers[l - 1];
+          pro.slabs = w.slabs, pro.nslab = splits, pro.b2_prev = pw.ff2_b, pro.g3 = pw.n3w, pro.b3 = pw.n3b;
+        }
+        DbWeights wt;
+        wt.stream = lw.blk_w;
+        wt.params = lw.blk_p;
+        // rows per block: DbOp<T>::ROWS (4: many small blocks spread a short search over the chip); a wide search -- R >= DB_WIDE_R
+        // rows, the grouped search of four 64-clip batches -- runs 8 rows per block (two per row wave): half the blocks, half the
+        // weight re-streaming from L2, +1.1 % end to end beside the encoder (profiles/r05_notes.md section 8).  Row-local arithmetic:
+        // the same bits either way.
+        auto launch_block = [&](auto nr_tag) -> int {
+          constexpr int NR = decltype(nr_tag)::value;
+          CN_TRY((cn_dec_block_setup<T, NR>()));
+          hipLaunchKernelGGL((cn_dec_block_kernel<T, NR>), dim3(cn_cdiv(R, NR)), dim3((DbL<T, NR>::THREADS)), (DbL<T, NR>::BYTES), s,
+                             pro, wt, kc, vc, anc, step, R, beam, maxp, (const T*)kvc, kv_ld, l * 2 * d, frame_lens, Ta, w.x,
+                             xt, scale, kvalid, db_debug, gate);
+          CN_LAUNCH_CHECK();
+          return CN_OK;
+        };
+        constexpr int kWide = CnIsH16<T>::value ? DB_WIDE_ROWS : DB_WIDE_ROWS_SP;
+        if (kWide != DbOp<T>::ROWS && R >= DB_WIDE_R) CN_TRY(launch_block(std::integral_constant<int, kWide>{}));
+        else CN_TRY(launch_block(std::integral_constant<int, DbOp<T>::ROWS>{}));
+      }
+      if (ffn_fused) {
+        CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+        CN_TRY(cn_dec_ffn_setup<T>());
+        hipLaunchKernelGGL(cn_dec_ffn_kernel<T>, dim3(dff / 256, cn_cdiv(R, DF_ROWS)), dim3(256), DF_LDS_BYTES_T(DbOp<T>::NPH), s, (const T*)xt, R,
+                           lw.ffn_w, lw.ff1_b, w.slabs, slab, gate);
+        CN_LAUNCH_CHECK();
+      } else if constexpr (CnIsH16<T>::value) {
+        {
+          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+          EpiBiasAct<T, ACT_GELU_FAST> e1{lw.ff1_b, ffh, dff, ACT_GELU_FAST};
+          CN_TRY(cn_gemm2(xt, d, (const T*)lw.ff1_w, d, R, dff, d, e1, s));
+        }
+        {
+          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+          EpiSlab e2{w.slabs, d, slab};
+          CN_TRY(cn_gemm2(ffh, dff, (const T*)lw.ff2_w, dff, R, d, dff, e2, s, splits));
+        }
+      }
+    }
+    {
+      CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
+      const CnLayerW& lw = ctx->layers[NL - 1];
+      hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.slabs, splits, slab, lw.ff2_b, w.x,
+                         lw.n3w, lw.n3b, R, w.x, xt);
+      CN_LAUNCH_CHECK();
+    }
+    {
+      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+      EpiBiasAct<float, ACT_NONE> ec{ctx->cls_b, w.logits, w.ldv, ACT_NONE};
+      CN_TRY(cn_mm(xt, d, (const T*)ctx->cls_w, d, R, V, d, ec, s));
+    }
+  }
+  if (!fused_done) {
+    auto self_attn = [&](int l) {
+      T* kc = (T*)w.kc + (size_t)l * maxp * R * d;
+      T* vc = (T*)w.vc + (size_t)l * maxp * R * d;
+      hipLaunchKernelGGL((cn_self_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.qkv, kc, vc, anc, step, R, beam, maxp,
+                         scale, (T*)w.attn_t, kvalid);
+    };
+    for (int l = 0; l < NL; ++l) CN_TRY((dec_sublayer_layer<T>(ctx, w, l, frame_lens, R, Ta, beam, kBlockT, self_attn, s)));
+    {
+      CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
+      EpiBiasAct<float, ACT_NONE> ec{ctx->cls_b, w.logits, w.ldv, ACT_NONE};
+      CN_TRY(cn_mm(xt, d, (const T*)ctx->cls_w, d, R, V, d, ec, s));
+    }
+  }
+  return CN_OK;
+}
+
+template <typename T>
+static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
+  const conette_config& cfg = ctx->cfg;
+  const int B = a.B, Ta = a.Ta, beam = a.beam, min_pred = a.min_pred, maxp = a.maxp;
+  const int R = B * beam, V = cfg.vocab_size;
+  DecWs w = dec_ws(ctx, B, Ta, beam, maxp, a.ws);
+  const bool forcing = a.force_caps != nullptr;
+  const bool sampling = a.uniforms != nullptr;
+  const unsigned long long* kvalid = forcing ? w.kvalid : nullptr;
 
   CN_TRY(dec_prepare<T>(ctx, a.frame_embs, B, Ta, w, s));
   hipLaunchKernelGGL(cn_init_state_kernel, dim3(64), dim3(256), 0, s, B, beam, maxp, a.bos_ids, w.n_active, w.slot,
@@ -315,111 +445,11 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
       hipLaunchKernelGGL(cn_force_tok_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, a.force_caps, B, maxp, step, w.cur_tok);
       CN_LAUNCH_CHECK();
     }
-    // fused path (dec_block.h + dec_ffn.h): 16-bit operands, and since round 4 the exact precision (hi / lo passes of the same
-    // two kernels; needs both packed streams, i.e. d_ff % 256 == 0 and d_ff <= 2048)
-    constexpr bool kBlockT = CnIsH16<T>::value || std::is_same<T, sp16_t>::value;
-    const bool block_path = kBlockT && !ctx->dec_unfused && ctx->layers[0].blk_w != nullptr &&
-                            (CnIsH16<T>::value || (ctx->layers[0].ffn_w != nullptr && dff / 256 <= FF2_SPLITS));
     // device-side early exit: once every hypothesis of every clip has finished the reference leaves its loop
     // (beam.py:192-194); the launch sequence is static (hipGraph), so the heavy kernels of the remaining steps read the
     // number of rows still searching and return at once
     const int* gate = (!forcing && step > 0) ? w.live + step : nullptr;
-    if (!block_path) {  // (the block path embeds in the prologue of layer 0's block kernel)
-      hipLaunchKernelGGL((cn_embed_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.cur_tok, ctx->emb, ctx->pe, step, 0, R,
-                         sqrtf((float)d), w.x, xt);
-      CN_LAUNCH_CHECK();
-    }
-    bool fused_done = false;
-    if constexpr (kBlockT) if (block_path) {
-      // default path: 3 launches per layer -- fused block (embedding | previous LN3, QKV, self-attention,
-      // cross-attention: dec_block.h), FFN1 GEMM + GELU, FFN2 split-K slabs (summed by the next layer's block
-      // prologue; the last layer's by the LN3 kernel in front of the classifier)
-      fused_done = true;
-      int splits = ff2_splits_default();
-      if (splits < 1 || splits > FF2_SPLITS || splits > 8 || dff % (splits * 64) != 0) splits = 1;
-      // fused FFN (dec_ffn.h): one launch per layer, one slab per 256-wide hidden chunk
-      const bool ffn_fused = ctx->layers[0].ffn_w != nullptr && dff / 256 <= FF2_SPLITS;
-      if (ffn_fused) splits = dff / 256;
-      const size_t slab = (size_t)R * d;
-      for (int l = 0; l < NL; ++l) {
-        const CnLayerW& lw = ctx->layers[l];
-        T* kc = (T*)w.kc + (size_t)l * maxp * R * d;
-        T* vc = (T*)w.vc + (size_t)l * maxp * R * d;
-        {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_ATTN, s);
-          DbPrologue pro;
-          pro.tok = w.cur_tok, pro.emb = ctx->emb, pro.pe_row = ctx->pe + (size_t)step * d, pro.emb_scale = sqrtf((float)d);
-          pro.slabs = nullptr, pro.nslab = 0, pro.slab_stride = slab, pro.b2_prev = nullptr, pro.g3 = nullptr, pro.b3 = nullptr;
-          if (l > 0) {
-            const CnLayerW& pw = ctx->layers[l - 1];
-            pro.slabs = w.slabs, pro.nslab = splits, pro.b2_prev = pw.ff2_b, pro.g3 = pw.n3w, pro.b3 = pw.n3b;
-          }
-          DbWeights wt;
-          wt.stream = lw.blk_w;
-          wt.params = lw.blk_p;
-          // rows per block: DbOp<T>::ROWS (4: many small blocks spread a short search over the chip); a wide search -- R >= DB_WIDE_R
-          // rows, the grouped search of four 64-clip batches -- runs 8 rows per block (two per row wave): half the blocks, half the
-          // weight re-streaming from L2, +1.1 % end to end beside the encoder (profiles/r05_notes.md section 8).  Row-local arithmetic:
-          // the same bits either way.
-          auto launch_block = [&](auto nr_tag) -> int {
-            constexpr int NR = decltype(nr_tag)::value;
-            CN_TRY((cn_dec_block_setup<T, NR>()));
-            hipLaunchKernelGGL((cn_dec_block_kernel<T, NR>), dim3(cn_cdiv(R, NR)), dim3((DbL<T, NR>::THREADS)), (DbL<T, NR>::BYTES), s,
-                               pro, wt, kc, vc, w.anc, step, R, beam, maxp, (const T*)kvc, kv_ld, l * 2 * d, a.frame_lens, Ta, w.x,
-                               xt, scale, kvalid, db_debug, gate);
-            CN_LAUNCH_CHECK();
-            return CN_OK;
-          };
-          constexpr int kWide = CnIsH16<T>::value ? DB_WIDE_ROWS : DB_WIDE_ROWS_SP;
-          if (kWide != DbOp<T>::ROWS && R >= DB_WIDE_R) CN_TRY(launch_block(std::integral_constant<int, kWide>{}));
-          else CN_TRY(launch_block(std::integral_constant<int, DbOp<T>::ROWS>{}));
-        }
-        if (ffn_fused) {
-          CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-          CN_TRY(cn_dec_ffn_setup<T>());
-          hipLaunchKernelGGL(cn_dec_ffn_kernel<T>, dim3(dff / 256, cn_cdiv(R, DF_ROWS)), dim3(256), DF_LDS_BYTES_T(DbOp<T>::NPH), s, (const T*)xt, R,
-                             lw.ffn_w, lw.ff1_b, w.slabs, slab, gate);
-          CN_LAUNCH_CHECK();
-        } else if constexpr (CnIsH16<T>::value) {
-          {
-            CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-            EpiBiasAct<T, ACT_GELU_FAST> e1{lw.ff1_b, ffh, dff, ACT_GELU_FAST};
-            CN_TRY(cn_gemm2(xt, d, (const T*)lw.ff1_w, d, R, dff, d, e1, s));
-          }
-          {
-            CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-            EpiSlab e2{w.slabs, d, slab};
-            CN_TRY(cn_gemm2(ffh, dff, (const T*)lw.ff2_w, dff, R, d, dff, e2, s, splits));
-          }
-        }
-      }
-      {
-        CnProfScope ps(ctx, CONETTE_PROF_DEC_MISC, s);
-        const CnLayerW& lw = ctx->layers[NL - 1];
-        hipLaunchKernelGGL((cn_ln256_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.slabs, splits, slab, lw.ff2_b, w.x,
-                           lw.n3w, lw.n3b, R, w.x, xt);
-        CN_LAUNCH_CHECK();
-      }
-      {
-        CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-        EpiBiasAct<float, ACT_NONE> ec{ctx->cls_b, w.logits, w.ldv, ACT_NONE};
-        CN_TRY(cn_mm(xt, d, (const T*)ctx->cls_w, d, R, V, d, ec, s));
-      }
-    }
-    if (!fused_done) {
-      auto self_attn = [&](int l) {
-        T* kc = (T*)w.kc + (size_t)l * maxp * R * d;
-        T* vc = (T*)w.vc + (size_t)l * maxp * R * d;
-        hipLaunchKernelGGL((cn_self_attn_kernel<T>), dim3(rblocks), dim3(256), 0, s, w.qkv, kc, vc, w.anc, step, R, beam, maxp,
-                           scale, (T*)w.attn_t, kvalid);
-      };
-      for (int l = 0; l < NL; ++l) CN_TRY((dec_sublayer_layer<T>(ctx, w, l, a.frame_lens, R, Ta, beam, kBlockT, self_attn, s)));
-      {
-        CnProfScope ps(ctx, CONETTE_PROF_DEC_GEMM, s);
-        EpiBiasAct<float, ACT_NONE> ec{ctx->cls_b, w.logits, w.ldv, ACT_NONE};
-        CN_TRY(cn_mm(xt, d, (const T*)ctx->cls_w, d, R, V, d, ec, s));
-      }
-    }
+    CN_TRY(dec_step_forward<T>(ctx, w, w.cur_tok, w.anc, gate, kvalid, a.frame_lens, B, Ta, beam, maxp, step, db_debug, s));
     if (step == 0 && a.step0_logits)
       CN_HIP(hipMemcpyAsync(a.step0_logits, w.logits, (size_t)R * w.ldv * 4, hipMemcpyDeviceToDevice, s));
     if (forcing) {
@@ -608,6 +638,27 @@ static int dec_check_workspace(const char* who, size_t workspace_bytes, size_t n
   return CN_OK;
 }
 
+// conette_decode and conette_decode_ensemble share their checks.  dec_check_search: the arguments every member of a search shares;
+// dec_check_member: what a context and its workspace must satisfy (one call per member).
+static int dec_check_search(const char* who, const int32_t* frame_lens, int batch, int t_audio, int beam, int min_pred, int max_pred,
+                            const int32_t* best_preds, const float* best_lprobs, const int32_t* mult_preds, const float* mult_lprobs,
+                            const int32_t* out_sizes) {
+  if (!frame_lens || !best_preds || !best_lprobs || !mult_preds || !mult_lprobs || !out_sizes || batch <= 0 || t_audio <= 0) {
+    cn_set_error("%s: bad argument", who);
+    return CN_ERR_ARG;
+  }
+  if (beam < 1 || beam > CN_MAX_BEAM || max_pred < 1 || max_pred > CN_MAX_PRED || min_pred < 0) {
+    cn_set_error("%s: beam=%d (1..%d) max_pred=%d (1..%d) min_pred=%d unsupported", who, beam, CN_MAX_BEAM, max_pred, CN_MAX_PRED,
+                 min_pred);
+    return CN_ERR_ARG;
+  }
+  return CN_OK;
+}
+static int dec_check_member(const char* who, const conette_ctx* ctx, int min_pred, int max_pred, size_t workspace_bytes, size_t need) {
+  CN_TRY(dec_check_model(ctx, who, max_pred, min_pred, "%s: max_pred exceeds positional table", who));
+  return dec_check_workspace(who, workspace_bytes, need);
+}
+
 // `run` (the launch sequence of the decode that `key` identifies) through the context's graph cache: eagerly at the first sighting
 // of a key, captured at the second, replayed from then on.
 template <typename Run>
@@ -716,18 +767,13 @@ extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const i
                               float* best_lprobs, int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes,
                               float* step0_logits, int32_t* trace_sel, float* trace_val, float* margins,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (!ctx || !frame_embs || !frame_lens || !bos_ids || !best_preds || !best_lprobs || !mult_preds || !mult_lprobs ||
-      !out_sizes || !workspace || batch <= 0 || t_audio <= 0) {
+  if (!ctx || !frame_embs || !bos_ids || !workspace) {
     cn_set_error("decode: bad argument");
     return CN_ERR_ARG;
   }
-  if (beam < 1 || beam > CN_MAX_BEAM || max_pred < 1 || max_pred > CN_MAX_PRED || min_pred < 0) {
-    cn_set_error("decode: beam=%d (1..%d) max_pred=%d (1..%d) min_pred=%d unsupported", beam, CN_MAX_BEAM, max_pred,
-                 CN_MAX_PRED, min_pred);
-    return CN_ERR_ARG;
-  }
-  CN_TRY(dec_check_model(ctx, "decode", max_pred, min_pred, "decode: max_pred exceeds positional table"));
-  CN_TRY(dec_check_workspace("decode", workspace_bytes, conette_decode_workspace_bytes(ctx, batch, t_audio, beam, max_pred)));
+  CN_TRY(dec_check_search("decode", frame_lens, batch, t_audio, beam, min_pred, max_pred, best_preds, best_lprobs, mult_preds, mult_lprobs,
+                          out_sizes));
+  CN_TRY(dec_check_member("decode", ctx, min_pred, max_pred, workspace_bytes, conette_decode_workspace_bytes(ctx, batch, t_audio, beam, max_pred)));
   DecArgs a;
   memset(&a, 0, sizeof(a));  // (padding included: the record is the graph key)
   a.frame_embs = frame_embs, a.frame_lens = frame_lens, a.bos_ids = bos_ids, a.forbid = forbid_mask;
@@ -737,6 +783,152 @@ extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const i
   a.B = batch, a.Ta = t_audio, a.beam = beam, a.min_pred = min_pred, a.maxp = max_pred;
   hipStream_t s = (hipStream_t)stream;
   return dec_graph_run(ctx, a, s, [&]() -> int { CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, s)); });
+}
+
+// ---- ensemble beam search (dec_ensemble.h): M members decode one hypothesis tree in lockstep ----------------------------------
+// Every member has its own workspace (dec_ws: activations, KV cache, cross K/V, logits); the search state lives in member 0's, and
+// the other members' block / attention kernels read it from there.  Per step: every member's forward, one after another on the
+// caller's stream, then ONE search step over the M logits arrays.  With one member the launch sequence is conette_decode's but for
+// the step kernel.
+__global__ void cn_ens_tok0_kernel(int R, int beam, const int* __restrict__ bos, int* __restrict__ tok) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < R) tok[i] = bos[i / beam];
+}
+
+template <typename T>
+static int decode_ensemble_impl(const DecArgs& a, hipStream_t s) {
+  const int M = a.n_members, B = a.B, Ta = a.Ta, beam = a.beam, maxp = a.maxp, R = B * beam;
+  conette_ctx* c0 = a.ens_ctx[0];
+  const conette_config& cfg = c0->cfg;
+  DecWs w[CN_MAX_MEMBERS];
+  for (int m = 0; m < M; ++m) {
+    w[m] = dec_ws(a.ens_ctx[m], B, Ta, beam, maxp, a.ens_ws[m]);
+    CN_TRY(dec_prepare<T>(a.ens_ctx[m], a.ens_fe[m], B, Ta, w[m], s));
+  }
+  hipLaunchKernelGGL(cn_init_state_kernel, dim3(64), dim3(256), 0, s, B, beam, maxp, a.ens_bos[0], w[0].n_active, w[0].slot,
+                     w[0].sum_lp, w[0].prefix, w[0].anc, w[0].cur_tok, a.mult_preds, a.mult_lprobs, w[0].out_len, a.out_sizes, cfg.pad_id,
+                     a.trace_sel, a.trace_val, w[0].live, a.margins);
+  CN_LAUNCH_CHECK();
+  for (int m = 1; m < M; ++m) {  // step 0: a member embeds its own task tokens (kept in its own workspace)
+    hipLaunchKernelGGL(cn_ens_tok0_kernel, dim3(cn_cdiv(R, 256)), dim3(256), 0, s, R, beam, a.ens_bos[m], w[m].cur_tok);
+    CN_LAUNCH_CHECK();
+  }
+  SsArgs ss;
+  ss.logits = nullptr, ss.forbid = a.forbid, ss.n_active = w[0].n_active, ss.slot = w[0].slot, ss.sum_lp = w[0].sum_lp;
+  ss.prefix = w[0].prefix, ss.anc = w[0].anc, ss.cur_tok = w[0].cur_tok, ss.out_preds = a.mult_preds, ss.out_avg = a.mult_lprobs;
+  ss.out_len = w[0].out_len, ss.trace_sel = a.trace_sel, ss.trace_val = a.trace_val, ss.live = w[0].live, ss.margins = a.margins;
+  ss.ldv = w[0].ldv, ss.V = cfg.vocab_size, ss.beam = beam, ss.maxp = maxp, ss.min_pred = a.min_pred, ss.eos_id = cfg.eos_id, ss.dbg = 0;
+  EsArgs es;
+  memset(&es, 0, sizeof(es));
+  for (int m = 0; m < M; ++m) {
+    es.logits[m] = w[m].logits, es.bos[m] = a.ens_bos[m], es.w[m] = a.ens_w[m];
+    es.logw[m] = (float)log((double)a.ens_w[m]);
+  }
+  es.comb = (float*)(a.ens_ws[0] + w[0].total);  // behind the plain search's workspace
+  es.M = M, es.rule = a.combine;
+  const size_t lbytes = (size_t)R * w[0].ldv * 4;
+  for (int step = 0; step < maxp; ++step) {
+    const int* gate = step > 0 ? w[0].live + step : nullptr;
+    for (int m = 0; m < M; ++m) {
+      const int* tok = (step == 0 && m > 0) ? w[m].cur_tok : w[0].cur_tok;
+      CN_TRY(dec_step_forward<T>(a.ens_ctx[m], w[m], tok, w[0].anc, gate, nullptr, a.frame_lens, B, Ta, beam, maxp, step, 0, s));
+      if (a.ens_step_logits)
+        CN_HIP(hipMemcpyAsync((char*)a.ens_step_logits + ((size_t)step * M + m) * lbytes, w[m].logits, lbytes, hipMemcpyDeviceToDevice, s));
+    }
+    CnProfScope ps_search(c0, CONETTE_PROF_SEARCH, s);
+    cn_ens_step_launch(ss, es, B, step, s);
+    CN_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(cn_finalize_kernel, dim3(cn_cdiv(B, 64)), dim3(64), 0, s, B, beam, maxp, cfg.eos_id, a.mult_preds,
+                     a.mult_lprobs, w[0].out_len, a.best_preds, a.best_lprobs, w[0].eos_idx, a.out_sizes, a.margins);
+  CN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cn_finalize2_kernel, dim3(1), dim3(256), 0, s, B, w[0].eos_idx, a.out_sizes);
+  CN_LAUNCH_CHECK();
+  return CN_OK;
+}
+
+extern "C" size_t conette_decode_ensemble_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t beam,
+                                                          int32_t max_pred) {
+  if (!ctx || batch <= 0 || t_audio <= 0 || max_pred <= 0 || beam < 1 || beam > CN_MAX_BEAM) return 0;
+  const DecWs w = dec_ws(ctx, batch, t_audio, beam, max_pred, nullptr);
+  return w.total + cn_align((size_t)batch * beam * w.ldv * 4);  // (+ the combined scores of the generic step: used in member 0's)
+}
+
+extern "C" int conette_decode_ensemble(const conette_member* members, int32_t n_members, int32_t combine, const int32_t* frame_lens,
+                                       const uint8_t* forbid_mask, int32_t batch, int32_t t_audio, int32_t beam, int32_t min_pred,
+                                       int32_t max_pred, int32_t* best_preds, float* best_lprobs, int32_t* mult_preds,
+                                       float* mult_lprobs, int32_t* out_sizes, int32_t* trace_sel, float* trace_val, float* margins,
+                                       float* step_logits, void* stream) {
+  const char* who = "decode_ensemble";
+  if (!members || n_members < 1 || n_members > CN_MAX_MEMBERS) {
+    cn_set_error("%s: n_members=%d unsupported (1..%d, members given)", who, n_members, CN_MAX_MEMBERS);
+    return CN_ERR_ARG;
+  }
+  if (combine != CONETTE_COMBINE_LOGPROB && combine != CONETTE_COMBINE_PROB) {
+    cn_set_error("%s: combine=%d unknown (0: logprob, 1: prob)", who, combine);
+    return CN_ERR_ARG;
+  }
+  for (int m = 0; m < n_members; ++m) {
+    const conette_member& mb = members[m];
+    const char* missing = !mb.ctx ? "ctx" : (!mb.frame_embs ? "frame_embs" : (!mb.bos_ids ? "bos_ids" : (!mb.workspace ? "workspace" : nullptr)));
+    if (missing) {
+      cn_set_error("%s: members[%d].%s is NULL", who, m, missing);
+      return CN_ERR_ARG;
+    }
+    if (!(mb.weight > 0.f) || !(mb.weight < INFINITY)) {
+      cn_set_error("%s: members[%d].weight=%g must be finite and > 0", who, m, (double)mb.weight);
+      return CN_ERR_ARG;
+    }
+  }
+  CN_TRY(dec_check_search(who, frame_lens, batch, t_audio, beam, min_pred, max_pred, best_preds, best_lprobs, mult_preds, mult_lprobs,
+                          out_sizes));
+  const conette_config& c0 = members[0].ctx->cfg;
+  for (int m = 0; m < n_members; ++m) {
+    const conette_config& c = members[m].ctx->cfg;
+    if (c.vocab_size != c0.vocab_size || c.eos_id != c0.eos_id || c.pad_id != c0.pad_id) {
+      cn_set_error("%s: members[%d].ctx has vocab_size=%d eos_id=%d pad_id=%d, members[0].ctx %d / %d / %d (one vocabulary per ensemble)", who,
+                   m, c.vocab_size, c.eos_id, c.pad_id, c0.vocab_size, c0.eos_id, c0.pad_id);
+      return CN_ERR_ARG;
+    }
+    if (c.precision != c0.precision) {
+      cn_set_error("%s: members[%d].ctx has precision %d, members[0].ctx %d (one precision per ensemble)", who, m, c.precision, c0.precision);
+      return CN_ERR_ARG;
+    }
+    CN_TRY(dec_check_member(who, members[m].ctx, min_pred, max_pred, members[m].workspace_bytes,
+                            conette_decode_ensemble_workspace_bytes(members[m].ctx, batch, t_audio, beam, max_pred)));
+    // a member keeps its KV cache, activations and logits in its workspace: two members on one range would overwrite each other's
+    const char* lo = (const char*)members[m].workspace;
+    const char* hi = lo + conette_decode_ensemble_workspace_bytes(members[m].ctx, batch, t_audio, beam, max_pred);
+    for (int o = 0; o < m; ++o) {
+      const char* olo = (const char*)members[o].workspace;
+      const char* ohi = olo + conette_decode_ensemble_workspace_bytes(members[o].ctx, batch, t_audio, beam, max_pred);
+      if (lo < ohi && olo < hi) {
+        cn_set_error("%s: members[%d].workspace overlaps members[%d].workspace (every member needs its own)", who, m, o);
+        return CN_ERR_ARG;
+      }
+    }
+  }
+  DecArgs a;
+  memset(&a, 0, sizeof(a));  // (padding included: the record is the graph key)
+  a.frame_lens = frame_lens, a.forbid = forbid_mask;
+  a.best_preds = best_preds, a.best_lprobs = best_lprobs, a.mult_preds = mult_preds, a.mult_lprobs = mult_lprobs;
+  a.out_sizes = out_sizes, a.trace_sel = trace_sel, a.trace_val = trace_val, a.margins = margins;
+  a.B = batch, a.Ta = t_audio, a.beam = beam, a.min_pred = min_pred, a.maxp = max_pred;
+  a.n_members = n_members, a.combine = combine, a.ens_step_logits = step_logits;
+  bool profiled = false;
+  for (int m = 0; m < n_members; ++m) {
+    a.ens_ctx[m] = members[m].ctx, a.ens_serial[m] = members[m].ctx->serial, a.ens_fe[m] = members[m].frame_embs;
+    a.ens_bos[m] = members[m].bos_ids, a.ens_ws[m] = (char*)members[m].workspace, a.ens_w[m] = members[m].weight;
+    a.ens_unfused[m] = members[m].ctx->dec_unfused;
+    profiled |= members[m].ctx->prof_mask != 0;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  auto run = [&]() -> int { CN_BY_PRECISION(a.ens_ctx[0], decode_ensemble_impl<OT>(a, s)); };
+  if (profiled) return run();  // (a profiled member's event pairs do not go into a captured graph)
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  CN_HIP(hipStreamIsCapturing(s, &cap));
+  if (cap != hipStreamCaptureStatusNone) return run();  // the caller captures: the launches go into the caller's graph
+  return dec_graph_run(a.ens_ctx[0], a, s, run);
 }
 
 extern "C" int32_t conette_decode_graph_nodes(const conette_ctx* ctx) {

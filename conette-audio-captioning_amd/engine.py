@@ -36,6 +36,7 @@ EXPORTS = (
     "conette_align_workspace_bytes", "conette_align", "conette_decode_groups_workspace_bytes", "conette_decode_groups",
     "conette_decode_constrained_workspace_bytes", "conette_decode_constrained",
     "conette_decode_required_workspace_bytes", "conette_decode_required",
+    "conette_decode_ensemble_workspace_bytes", "conette_decode_ensemble",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -92,6 +93,12 @@ class ConetteConfigC(C.Structure):
 class EncodeTapsC(C.Structure):
     _fields_ = [("struct_bytes", C.c_size_t), ("logmel", C.c_void_p), ("stem", C.c_void_p), ("stage_block0", C.c_void_p * 4),
                 ("stage", C.c_void_p * 4), ("down", C.c_void_p * 4), ("block", C.c_void_p * 18)]
+
+
+class ConetteMemberC(C.Structure):
+    """conette_member (include/conette_hip.h): one member of a conette_decode_ensemble call"""
+    _fields_ = [("ctx", C.c_void_p), ("frame_embs", C.c_void_p), ("bos_ids", C.c_void_p), ("weight", C.c_float),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 _lib = None
@@ -176,6 +183,12 @@ def load_library() -> C.CDLL:
                                             C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_decode_ensemble_workspace_bytes.restype = C.c_size_t
+    lib.conette_decode_ensemble_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_decode_ensemble.restype = C.c_int
+    lib.conette_decode_ensemble.argtypes = [C.POINTER(ConetteMemberC), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.conette_greedy_workspace_bytes.restype = C.c_size_t
     lib.conette_greedy_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.conette_greedy.restype = C.c_int
@@ -822,6 +835,80 @@ class Engine:
                                             _ptr(o["trace_val"]), _ptr(o["step_logits"]), _ptr(wsb), wsb.numel(), _stream())
         _check(st, "conette_decode_groups")
         return {k: v for k, v in o.items() if v is not None}
+
+    def decode_ensemble(self, members, frame_lens: torch.Tensor, forbid_mask: Optional[torch.Tensor], beam: int, min_pred: int,
+                        max_pred: int, combine: str = "logprob", want_trace: bool = False, want_logits: bool = False,
+                        want_margins: bool = False, clone: bool = True) -> Dict[str, torch.Tensor]:
+        """Ensemble beam search (conette_decode_ensemble, include/conette_hip.h; the rule: ensemble_search.py).  ``members``: a list
+        of (engine, frame_embs (B, T, 768), bos_ids (B,), weight) -- the same engine may appear more than once (one checkpoint under
+        several task tokens); the weights are normalised to sum 1 here.  The members decode one hypothesis tree in lockstep and the
+        top-k runs on the combined scores (``combine`` "logprob": sum_m w_m lp_m; "prob": log sum_m w_m exp lp_m).  Returns
+        ``decode``'s dict [, "trace_sel", "trace_val"] [, "margins"] [, "step_logits" (max_pred, M, B * beam, vocab): every member's
+        raw logits as each step read them].  The I/O buffers and the members' workspaces are this engine's and persist per shape, so
+        the library replays its hipGraph; ``clone=False`` returns those buffers."""
+        from . import ensemble_search
+        members = list(members)
+        w64, rule = ensemble_search.check_arguments(len(members), [m[3] for m in members], combine, beam)
+        m_n, beam, max_pred = len(members), int(beam), int(max_pred)
+        b, t, _ = members[0][1].shape
+        for eng, fe, bos, _ in members:
+            if tuple(fe.shape) != (b, t, FEAT) or bos.numel() != b:
+                raise ValueError("members: every frame_embs must be (B, T, 768) of one shape, every bos_ids (B,)")
+            if eng.vocab_size != self.vocab_size or eng.eos_id != self.eos_id or eng.pad_id != self.pad_id:
+                raise ValueError("members: the engines must share the vocabulary size and the eos / pad ids")
+            if eng.precision_dec != members[0][0].precision_dec:
+                raise ValueError("members: the engines' decoders must share one precision")
+            if eng.device != self.device:
+                raise ValueError(f"members: an engine on {eng.device} in an ensemble run on {self.device} (one device per ensemble)")
+        key = ("ens", m_n, b, t, beam, max_pred, want_trace, want_logits, want_margins)
+        buf = self._dec_bufs.pop(key, None)
+        if buf is None:
+            dev = self.device
+            ldv = (self.vocab_size + 7) // 8 * 8
+            e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            buf = {"fe": [e((b, t, FEAT), torch.float32) for _ in range(m_n)], "bos": [e((b,), torch.int32) for _ in range(m_n)],
+                   "lens": e((b,), torch.int32), "forbid": e((self.vocab_size,), torch.uint8),
+                   "best_preds": e((b, max_pred), torch.int32), "best_lprobs": e((b,), torch.float32),
+                   "mult_preds": e((b, beam, max_pred), torch.int32), "mult_lprobs": e((b, beam), torch.float32),
+                   "sizes": e((2,), torch.int32),
+                   "trace_sel": e((max_pred, b, beam, 2), torch.int32) if want_trace else None,
+                   "trace_val": e((max_pred, b, beam), torch.float32) if want_trace else None,
+                   "margins": e((b, 2, max_pred + 1), torch.float32) if want_margins else None,
+                   "step_logits": e((max_pred, m_n, b * beam, ldv), torch.float32) if want_logits else None}
+            if len(self._dec_bufs) >= MAX_DECODE_GRAPHS:
+                torch.cuda.synchronize(self.device)     # (as _decode_buffers: the evicted buffers may still be in use)
+                self._dec_bufs.pop(next(iter(self._dec_bufs)))
+        self._dec_bufs[key] = buf
+        recs = (ConetteMemberC * m_n)()
+        for i, (eng, fe, bos, _) in enumerate(members):
+            if fe.data_ptr() != buf["fe"][i].data_ptr():
+                buf["fe"][i].copy_(fe, non_blocking=True)
+            buf["bos"][i].copy_(bos.to(torch.int32), non_blocking=True)
+            ctx = eng._ctx_dec
+            need = self.lib.conette_decode_ensemble_workspace_bytes(ctx, b, t, beam, max_pred)
+            wsb = self._workspace(f"ens{i}", need)
+            recs[i] = ConetteMemberC(ctx, buf["fe"][i].data_ptr(), buf["bos"][i].data_ptr(), float(w64[i]), wsb.data_ptr(),
+                                     wsb.numel())
+        buf["lens"].copy_(frame_lens.to(torch.int32), non_blocking=True)
+        forbid_ptr = None
+        if forbid_mask is not None:
+            if forbid_mask.numel() != self.vocab_size:
+                raise ValueError("forbid_mask must have vocab_size entries")
+            buf["forbid"].copy_(forbid_mask.to(torch.uint8), non_blocking=True)
+            forbid_ptr = buf["forbid"]
+        st = self.lib.conette_decode_ensemble(recs, m_n, rule, _ptr(buf["lens"]), _ptr(forbid_ptr), b, t, beam, int(min_pred), max_pred,
+                                              _ptr(buf["best_preds"]), _ptr(buf["best_lprobs"]), _ptr(buf["mult_preds"]),
+                                              _ptr(buf["mult_lprobs"]), _ptr(buf["sizes"]), _ptr(buf["trace_sel"]), _ptr(buf["trace_val"]),
+                                              _ptr(buf["margins"]), _ptr(buf["step_logits"]), _stream())
+        _check(st, "conette_decode_ensemble")
+        cp = (lambda x: x.clone()) if clone else (lambda x: x)
+        out = {k: cp(buf[k]) for k in ("best_preds", "best_lprobs", "mult_preds", "mult_lprobs", "sizes")}
+        for k in ("trace_sel", "trace_val", "margins"):
+            if buf[k] is not None:
+                out[k] = cp(buf[k])
+        if want_logits:
+            out["step_logits"] = cp(buf["step_logits"])[..., : self.vocab_size]
+        return out
 
     def decode_constrained(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, bos_ids: torch.Tensor,
                            forbid_mask: Optional[torch.Tensor], beam: int, min_pred: int, max_pred: int,

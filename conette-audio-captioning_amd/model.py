@@ -479,29 +479,72 @@ class CoNeTTEModel:
             clip_probs = keep.get("clip_probs")
             bsize = len(audio)
             tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
-            if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
-                bad = self.engine.encode_nonfinite()       # (include/conette_hip.h: conette_encode_nonfinite)
-                if bad:
-                    raise RuntimeError(
-                        f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
-                        "positions with non-finite LayerNorm statistics); use precision='exact' or 'fp32' for this checkpoint")
+            self._refuse_encoder_overflow(preprocess)
             cfg = self.config
             min_pred = cfg.min_pred_size if min_pred_size is None else int(min_pred_size)
             max_pred = cfg.max_pred_size if max_pred_size is None else int(max_pred_size)
             res = self.engine.decode_groups(audio, audio_shape[:, 1].to(torch.int32), self.batch_to_task_token_ids(dataset_lst, source_lst),
                                             self.get_forbid_rep_mask(forbid_rep_mode), g, w, float(diversity_penalty), min_pred, max_pred)
-            pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())            # the one host sync
-            mult_preds = res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous()
-            preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()
-            outs = {
-                "cands": self.tokenizer.decode_rec(preds), "preds": preds, "lprobs": res["best_lprobs"],
-                "mult_cands": self.tokenizer.decode_rec(mult_preds), "mult_preds": mult_preds, "mult_lprobs": res["mult_lprobs"],
-                "tasks": tasks,
-            }
-            if clip_probs is not None:
-                outs["tags_probs"] = clip_probs
-                outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
-            return outs
+            return self._search_outputs(res, tasks, clip_probs, threshold)
+
+    def _refuse_encoder_overflow(self, preprocess: bool) -> None:
+        """After an encode of a search that has no exact re-run: an overflow of the 16-bit encoders' fp16 residual stream raises."""
+        if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
+            bad = self.engine.encode_nonfinite()       # (include/conette_hip.h: conette_encode_nonfinite)
+            if bad:
+                raise RuntimeError(
+                    f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
+                    "positions with non-finite LayerNorm statistics); use precision='exact' or 'fp32' for this checkpoint")
+
+    def _search_outputs(self, res: Dict[str, Tensor], tasks: List[str], clip_probs, threshold) -> Dict[str, Any]:
+        """``forward``'s keys from a search's device outputs (best_* / mult_* / sizes)."""
+        pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())            # the one host sync
+        mult_preds = res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous()
+        preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()
+        outs = {
+            "cands": self.tokenizer.decode_rec(preds), "preds": preds, "lprobs": res["best_lprobs"],
+            "mult_cands": self.tokenizer.decode_rec(mult_preds), "mult_preds": mult_preds, "mult_lprobs": res["mult_lprobs"],
+            "tasks": tasks,
+        }
+        if clip_probs is not None:
+            outs["tags_probs"] = clip_probs
+            outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
+        return outs
+
+    @torch.no_grad()
+    def caption_ensemble(self, x, tasks: Union[str, List[str]], weights: Optional[List[float]] = None, combine: str = "logprob",
+                         beam_size: Optional[int] = None, sr=None, x_shapes=None, preprocess: bool = True,
+                         min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
+                         forbid_rep_mode: Optional[str] = None, threshold: Union[float, Tensor] = 0.3) -> Dict[str, Any]:
+        """ONE caption per clip that several task tokens agree on: a task ensemble on the device (conette_decode_ensemble; the
+        rule: ensemble_search.py).  One encode; one member per entry of ``tasks`` (1 .. 4 task names, each applied to every clip),
+        all members decoding one hypothesis tree, the top-k running on the combined scores -- ``combine="logprob"``: the
+        ``weights``-weighted mean of the members' log-probabilities (a product of experts), ``"prob"``: the log of the weighted mean
+        of their probabilities (a mixture); ``weights`` are normalised to sum 1 (None: equal).  ``x`` and the size / mask arguments
+        as in ``forward``, whose keys it returns; "tasks" holds the members' tasks joined by "+" for every clip, the scores are
+        the combined ones.  With one task this is ``forward`` under that task.  Precision "certified*" and the mixed precisions run
+        this search on the base pipeline's decoder context, with no exact re-run: no certificate is defined for it.  With
+        waveforms in, an overflow of the 16-bit encoders' fp16 residual stream raises as in ``caption_diverse``."""
+        from . import ensemble_search
+        names = [tasks] if isinstance(tasks, str) else list(tasks)
+        cfg = self.config
+        beam = cfg.beam_size if beam_size is None else int(beam_size)
+        w, _ = ensemble_search.check_arguments(len(names), weights, combine, beam)
+        with torch.cuda.device(self.device):
+            keep: dict = {}
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess, keep)
+            audio_shape = torch.as_tensor(audio_shape)
+            bsize = len(audio)
+            self._refuse_encoder_overflow(preprocess)
+            members = []
+            for name, wt in zip(names, w):
+                _, dataset_lst, source_lst = self._split_tasks(name, bsize)
+                members.append((self.engine, audio, self.batch_to_task_token_ids(dataset_lst, source_lst), float(wt)))
+            min_pred = cfg.min_pred_size if min_pred_size is None else int(min_pred_size)
+            max_pred = cfg.max_pred_size if max_pred_size is None else int(max_pred_size)
+            res = self.engine.decode_ensemble(members, audio_shape[:, 1].to(torch.int32), self.get_forbid_rep_mask(forbid_rep_mode), beam,
+                                              min_pred, max_pred, combine=combine)
+            return self._search_outputs(res, ["+".join(names)] * bsize, keep.get("clip_probs"), threshold)
 
     def required_groups(self, required, required_per_clip, bsize: int) -> List[List[List[int]]]:
         """per clip the requirement groups (token lists) of ``caption_constrained``'s ``required`` / ``required_per_clip``"""
@@ -564,12 +607,7 @@ class CoNeTTEModel:
             clip_probs = keep.get("clip_probs")
             bsize = len(audio)
             tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
-            if preprocess and self.engine.precision in (PREC_BF16, PREC_F16):
-                bad = self.engine.encode_nonfinite()       # (include/conette_hip.h: conette_encode_nonfinite)
-                if bad:
-                    raise RuntimeError(
-                        f"precision={self.engine.precision_name!r}: the encoder's fp16 residual stream overflowed ({bad} "
-                        "positions with non-finite LayerNorm statistics); use precision='exact' or 'fp32' for this checkpoint")
+            self._refuse_encoder_overflow(preprocess)
             cfg, tok = self.config, self.tokenizer
             beam = cfg.beam_size if beam_size is None else int(beam_size)
             min_pred = cfg.min_pred_size if min_pred_size is None else int(min_pred_size)
@@ -618,18 +656,7 @@ class CoNeTTEModel:
                 res = self.engine.decode_required(audio, audio_shape[:, 1].to(torch.int32), bos, forbid, w, min_pred, max_pred,
                                                   prefix=table, prefix_lens=lens, ban_mask=ban, no_repeat_ngram=n,
                                                   req_tokens=torch.from_numpy(rt), req_groups=torch.from_numpy(rg), check=False)
-            pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())            # the one host sync
-            mult_preds = res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous()
-            preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()
-            outs = {
-                "cands": self.tokenizer.decode_rec(preds), "preds": preds, "lprobs": res["best_lprobs"],
-                "mult_cands": self.tokenizer.decode_rec(mult_preds), "mult_preds": mult_preds, "mult_lprobs": res["mult_lprobs"],
-                "tasks": tasks,
-            }
-            if clip_probs is not None:
-                outs["tags_probs"] = clip_probs
-                outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
-            return outs
+            return self._search_outputs(res, tasks, clip_probs, threshold)
 
     def teacher_forcing(self, x, caps_in: Tensor, sr=None, x_shapes=None, preprocess: bool = True) -> Tensor:
         """CoNeTTEPLM.decode_audio(encode_audio(...), "forcing", caps_in=caps_in) (pl_modules/conette.py:392-417,

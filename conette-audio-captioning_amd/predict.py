@@ -75,6 +75,15 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
     parser.add_argument("--require_words", type=str, nargs="+", default=None,
                         help="Words every caption must hold (CoNeTTEModel.caption_constrained(required=...)); 'bark|barks' asks for "
                              "one of the alternatives.")
+    parser.add_argument("--ensemble_models", type=str, nargs="+", default=None,
+                        help="2 .. 4 local HF directories: their models caption as one ensemble (one search, combined scores); "
+                             "in place of --model_name / --model_path.")
+    parser.add_argument("--ensemble_tasks", type=str, nargs="+", default=None,
+                        help="Task ensemble: one caption that these tasks agree on (with --ensemble_models: one task per model).")
+    parser.add_argument("--ensemble_weights", type=float, nargs="+", default=None,
+                        help="With --ensemble_models / --ensemble_tasks: one positive weight per member (normalised; default equal).")
+    parser.add_argument("--ensemble_combine", type=str, choices=("logprob", "prob"), default="logprob",
+                        help="With --ensemble_models / --ensemble_tasks: logprob (product of experts) or prob (mixture).")
     parser.add_argument("--csv_export", type=_opt_str, help="Path to CSV output file.", default=None)
     parser.add_argument("--verbose", type=int, help="Verbose level.", default=1)
     parser.add_argument("--precision", type=str, default=None,
@@ -89,6 +98,27 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
         for flag, on in (("--sample", args.sample > 0), ("--beam_groups", args.beam_groups > 0), ("--align", args.align)):
             if on:
                 raise ValueError(f"--prefix / --ban_words / --no_repeat_ngram / --require_words steer the beam search; they do not go with {flag}")
+    ensemble = args.ensemble_models is not None or args.ensemble_tasks is not None
+    if not ensemble and args.ensemble_weights is not None:
+        raise ValueError("--ensemble_weights goes with --ensemble_models or --ensemble_tasks")
+    if ensemble:
+        steered = args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0 or args.require_words is not None
+        for flag, on in (("--sample", args.sample > 0), ("--beam_groups", args.beam_groups > 0), ("--align", args.align),
+                         ("--prefix / --ban_words / --no_repeat_ngram / --require_words", steered), ("--task", args.task is not None)):
+            if on:
+                raise ValueError(f"--ensemble_models / --ensemble_tasks run the plain beam search on combined scores; they do not go with {flag}")
+        if args.ensemble_models is not None:
+            if args.model_path is not None or args.model_name != parser.get_default("model_name"):
+                raise ValueError("--ensemble_models names the models; it does not go with --model_name / --model_path")
+            if not 2 <= len(args.ensemble_models) <= 4:
+                raise ValueError(f"--ensemble_models: {len(args.ensemble_models)} directories (expected 2 .. 4; one model: --model_name)")
+        n = len(args.ensemble_models) if args.ensemble_models is not None else len(args.ensemble_tasks)
+        if args.ensemble_models is not None and args.ensemble_tasks is not None and len(args.ensemble_tasks) not in (1, n):
+            raise ValueError(f"--ensemble_tasks: {len(args.ensemble_tasks)} tasks for {n} --ensemble_models (expected one, or one per model)")
+        if args.ensemble_weights is not None and len(args.ensemble_weights) != n:
+            raise ValueError(f"--ensemble_weights: {len(args.ensemble_weights)} weights for {n} members")
+        from . import ensemble_search
+        ensemble_search.check_arguments(n, args.ensemble_weights, args.ensemble_combine, 1)
     return args
 
 
@@ -181,6 +211,20 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
     from .model import DEFAULT_PRECISION, CoNeTTEModel
 
     precision = DEFAULT_PRECISION if args.precision is None else args.precision
+    if args.ensemble_models is not None:     # several checkpoints, one search (ensemble.py)
+        from .ensemble import CoNeTTEEnsemble
+        models = [CoNeTTEModel.from_pretrained(d, config=CoNeTTEConfig.from_pretrained(d), device=args.device, precision=precision).eval_and_disable_grad()
+                  for d in args.ensemble_models]
+        ens = CoNeTTEEnsemble(models, weights=args.ensemble_weights, combine=args.ensemble_combine)
+        tasks = args.ensemble_tasks[0] if args.ensemble_tasks is not None and len(args.ensemble_tasks) == 1 else args.ensemble_tasks
+        fpaths = list(args.audio)
+        outs = ens(fpaths, task=tasks)
+        results = format_results(fpaths, outs["tasks"], outs["cands"])
+        for r in results:
+            pylog.info(f"File '{r['audio']}' with task '{r['task']}':\n - '{r['candidate']}'")
+        if args.csv_export is not None:
+            write_csv(args.csv_export, results)
+        return results
     if args.model_path is not None:     # (the reference gives model_path the precedence too: predict.py:196-201)
         config, sd = model_path_state_dict(args.model_path, args.encoder_ckpt)
         model = CoNeTTEModel(config, device=args.device, state_dict=sd, precision=precision)
@@ -205,7 +249,10 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         if args.csv_export is not None:
             write_csv(args.csv_export, results)
         return results
-    if args.beam_groups > 0:   # G x W captions per file, group-major
+    if args.ensemble_tasks is not None:   # one caption per file that the tasks agree on
+        outs = model.caption_ensemble(fpaths, tasks=args.ensemble_tasks, weights=args.ensemble_weights, combine=args.ensemble_combine)
+        results = format_results(fpaths, outs["tasks"], outs["cands"])
+    elif args.beam_groups > 0:   # G x W captions per file, group-major
         outs = model.caption_diverse(fpaths, num_groups=args.beam_groups, group_beam_size=args.group_beam,
                                      diversity_penalty=args.diversity_penalty, task=tasks)
         n = args.beam_groups * args.group_beam

@@ -305,6 +305,54 @@ int conette_decode_groups(conette_ctx* ctx, const float* frame_embs, const int32
                           int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes, int32_t* trace_sel, float* trace_val,
                           float* step_logits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Ensemble beam search: conette_decode at beam `beam` whose candidates are scored by M = n_members (1..4) members -- several
+ * checkpoints, or one checkpoint under several task tokens -- that decode ONE hypothesis tree in lockstep, the top-k running on the
+ * combined scores inside the one search-step launch per decode step (csrc/dec_ensemble.h; the CPU restatement of the rule is
+ * conette_amd/ensemble_search.py).
+ *   members     : host array of n_members records.  ctx: the member's context (the same context may appear more than once);
+ *                 frame_embs: dev (B, t_audio, 768) fp32, its audio memory; bos_ids: dev (B) int32, its task token per clip;
+ *                 weight: finite and > 0 -- the caller normalises the weights to sum 1 (the library uses them as given);
+ *                 workspace / workspace_bytes: its own, conette_decode_ensemble_workspace_bytes(ctx, ...) bytes; the members' ranges
+ *                 must not overlap (refused)
+ *   combine     : CONETTE_COMBINE_LOGPROB  c(p, v) = sum_m w_m * lp_m(p, v)            (product of experts; -inf where any member is)
+ *                 CONETTE_COMBINE_PROB     c(p, v) = log sum_m w_m * exp(lp_m(p, v))   (mixture; -inf only where every member is;
+ *                                          accumulated around a running maximum, so it never underflows where some lp_m is finite)
+ *                 with one member c = lp_0 under either rule, no arithmetic
+ *   lp_m(p, .)  = the log-softmax of member m's logits of candidate row p, masked as conette_decode masks them (EOS floor while
+ *                 step < min_pred, forbid-repeat over the row's prefix WITH MEMBER m's OWN TASK TOKEN at position 0): bit for bit what
+ *                 conette_decode's step computes for member m on that prefix
+ *   score       sum_lp[p] + c(p, v) (step 0: c); top-k over the k * V candidates, ties to the lowest flat index, finished picks to their
+ *               slot with score / (step + 1), the shortage rule: all conette_decode's.  The returned scores are the combined ones.
+ * Shared by the members: frame_lens, t_audio, forbid_mask, beam (1..16), min_pred, max_pred, and the vocabulary size, eos and pad ids
+ * and the precision of their contexts (a difference is an error).  Every decode step runs every member's forward on that member's
+ * workspace, one after another on `stream`, against the search state in member 0's workspace; at step 0 a member embeds its own
+ * task tokens, afterwards the shared current tokens.
+ * Outputs as conette_decode's (best_*, mult_*, out_sizes, optional trace_sel / trace_val / margins), and
+ *   step_logits : optional dev (max_pred, M, B * beam, ldv) fp32, ldv = vocab rounded up to a multiple of 8: the RAW (unmasked) logits
+ *                 of every member as they stood when that step decided (rows that no longer search are unspecified); or NULL
+ * With one member the result is conette_decode's bit for bit; so it is with 2 or 4 copies of one member (same context, same task
+ * tokens, separate workspaces) at equal weights under CONETTE_COMBINE_LOGPROB.  A failing call names the argument, launches nothing
+ * and leaves the outputs untouched.  Replayed from the decode graph cache of members[0].ctx (keyed on every member's context --
+ * pointer, creation serial and decode-fusion option --, buffers, workspace, weight and the rule); asynchronous on `stream`; bit-identical from run to
+ * run.  Works on decoder-only contexts and in every precision. */
+#define CONETTE_COMBINE_LOGPROB 0
+#define CONETTE_COMBINE_PROB 1
+typedef struct conette_member {
+  conette_ctx* ctx;
+  const float* frame_embs;
+  const int32_t* bos_ids;
+  float weight;
+  void* workspace;
+  size_t workspace_bytes;
+} conette_member;
+size_t conette_decode_ensemble_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio, int32_t beam,
+                                               int32_t max_pred); /* per member */
+int conette_decode_ensemble(const conette_member* members, int32_t n_members, int32_t combine, const int32_t* frame_lens,
+                            const uint8_t* forbid_mask, int32_t batch, int32_t t_audio, int32_t beam, int32_t min_pred,
+                            int32_t max_pred, int32_t* best_preds, float* best_lprobs, int32_t* mult_preds, float* mult_lprobs,
+                            int32_t* out_sizes, int32_t* trace_sel, float* trace_val, float* margins, float* step_logits,
+                            void* stream);
+
 /* Constrained beam search: conette_decode at beam W = `beam` (1..16) whose caller steers the search -- a forced beginning per
  * clip, tokens that never appear, no n-gram twice -- inside the one search-step launch per decode step (csrc/dec_constrain.h; the
  * CPU restatement of the rule is conette_amd/constrained_search.py).
