@@ -202,7 +202,9 @@ __global__ __launch_bounds__(FE_NW * 64) void cn_logmel_kernel(const float* __re
             for (int u = 0; u < 4; ++u) acc = fmaf(p[u], w[u], acc);
           }
           for (; i < trip; ++i) acc = fmaf(sp[min(lo + i, CN_N_BINS - 1)], mc[i * CN_N_MELS + m], acc);
-          const float db = 10.0f * log10f(fmaxf(acc, 1e-10f));
+          // clamp as torch.clamp(min=1e-10) does: a NaN band sum (a non-finite sample in the frame) stays NaN -- fmaxf would
+          // return the floor and report silence
+          const float db = 10.0f * log10f(acc < 1e-10f ? 1e-10f : acc);
           out[(size_t)fr * CN_N_MELS + m] = db * m_sc[g] + m_sh[g];
         }
       }
