@@ -9,6 +9,7 @@
 
 #include "ctx.h"
 #include <type_traits>
+#include <utility>
 
 // Overflow watch of the fp16 residual stream (round 6).  A stream value beyond 65504 is inf where the fused MLP stored it; the
 // saturating conversions further down the encoder then turn the NaNs of the next LayerNorm back into finite garbage, so the
@@ -129,8 +130,9 @@ __global__ __launch_bounds__(256) void cn_stem_mfma_kernel(const float* __restri
 // (XT = half_t: 2-byte loads feed v_fma_mix_f32 directly -- the fp16 input is an operand of the fp32 fma, no conversion
 // instruction, the same products and sums as from an fp32 stream holding the same values)
 // One thread = one channel x a TH(h) x 4(w) output patch: (TH+6) x 10 loads feed TH*4*49 FMAs.
-// Loads are branch-free (clamped address, zero-masked value) and issued a whole input row at a
-// time so that many are in flight; lanes run over channels, so every load instruction is one
+// Loads are issued a whole input row at a time so that many are in flight (fp16 stream: one pipelined body for every thread,
+// zero padding by the pack's selector and by skipping rows outside the map; fp32 stream: an interior path and a clamped-address,
+// zero-masked edge path); lanes run over channels, so every load instruction is one
 // coalesced 256-byte line.  The block is C x S threads covering a TH x (4S) tile for all
 // channels, so the LayerNorm over C is local to the block: conv results go through an LDS tile
 // [pos][C] and one wave normalises a position (two-pass mean / variance, wave-shuffle sums).
@@ -156,7 +158,18 @@ template <int C, int S, int TH> struct DwTile {
   static constexpr int PITCH = PITCH4 * 4;
 };
 
-template <typename T, typename XT, int C, int S, int TH>
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant inside every step
+template <int... U, typename F> __device__ __forceinline__ void cn_static_for(std::integer_sequence<int, U...>, F&& f) {
+  (f(std::integral_constant<int, U>{}), ...);
+}
+// An empty asm per accumulator (constant indices: the array stays in registers): the products written before it stay before
+// the loads written after it.  It emits no instruction; see the row-tested pipeline of cn_dwconv_ln_kernel.
+__device__ __forceinline__ void cn_dw_pin1(float& v) { asm volatile("" : "+v"(v) : : "memory"); }
+template <int TH, size_t... I> __device__ __forceinline__ void cn_dw_pin(float (&acc)[TH][4], std::index_sequence<I...>) {
+  (cn_dw_pin1(acc[I / 4][I % 4]), ...);
+}
+
+template <typename T, typename XT, int C, int S, int TH, bool CLAMPED = false>
 __global__ __launch_bounds__((C > 384 ? 384 : C) * S) void cn_dwconv_ln_kernel(const XT* __restrict__ x, int H, int W, int tiles_h,
                                                             int tiles_w, const float* __restrict__ dw_w /*[49][C]*/,
                                                             const unsigned* __restrict__ dw_wp /*[42][C] fp16 row pairs (fp16 stream)*/,
@@ -196,10 +209,12 @@ __global__ __launch_bounds__((C > 384 ? 384 : C) * S) void cn_dwconv_ln_kernel(c
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[a][e] = bias;
   const XT* xb = x + (size_t)b * H * W * C + c;
-  // 80 % of the tiles are interior: no clamping / masking, and every load of an input row is
-  // `row base + compile-time offset` (q * C floats fits the 13-bit immediate), which removes the
-  // per-load 64-bit address arithmetic that dominated the VALU instruction count (rocprof:
-  // 4250 VALU wave-instructions per 32-output patch against 1568 FMAs).
+  // fp32 stream: 78 % of the THREADS of the 10 s map are interior (no clamping / masking, every load of an input row is
+  // `row base + compile-time offset`: q * C floats fits the 13-bit immediate, which removes the per-load 64-bit address
+  // arithmetic that dominated the VALU instruction count -- rocprof: 4250 VALU wave-instructions per 32-output patch against
+  // 1568 FMAs).  Counted in TILES, which is what a block's time follows, 95 of 147 (stage 0, 12 x 8 tiles) and 45 of 77
+  // (stage 1, 12 x 4) hold no edge thread: 35 % / 42 % of the tiles have one.  The fp16 stream therefore has one body for
+  // every thread (below); only the fp32 stream still chooses per thread.
   const bool interior = (h0 >= 3) && (h0 + TH + 3 <= H) && (w0 >= 3) && (w0 + 4 + 3 <= W);
   if constexpr (sizeof(XT) == 2) {
     // ---- fp16 stream, round 5: input rows in PAIRS.  p[q] = (x[r][q], x[r + 1][q]) for even r is one register, the weights come as
@@ -238,24 +253,92 @@ __global__ __launch_bounds__((C > 384 ? 384 : C) * S) void cn_dwconv_ln_kernel(c
       }
     };
     constexpr int NPR = (TH + 6) / 2;
-    if (interior) {
-      const XT* base = xb + ((size_t)(h0 - 3) * W + (w0 - 3)) * C;
-      auto load_pair = [&](int r, cn_h2 (&p)[10]) {
-        const XT* x0 = base + (size_t)r * W * C;
-        const XT* x1 = x0 + (size_t)W * C;
+    if constexpr (!CLAMPED) {
+      // ---- ONE body for every thread: the two-pair software pipeline, loads with `uniform row base + per-thread offset + immediate`.
+      // Launched only where W is a multiple of the tile width 4 S and W >= 12 (launch_dwconv), so a thread's ten halo columns
+      // w0 - 3 .. w0 + 6 are all inside the map, or the first three are outside (w0 == 0), or the last three (w0 == W - 4).
+      // The columns go in three groups with a per-thread element offset from column 0 of a row each:
+      //   q = 0..2 at oL + q C, q = 3..6 at oM + (q - 3) C, q = 7..9 at oR + (q - 7) C.
+      // An outside group is moved three columns into the map -- oL to column 0 (w0 == 0), oR to column W - 3 (w0 == W - 4) --
+      // and its values are dropped by the pack: the v_perm that joins the two rows of a pair takes its selector from a
+      // register, and the selector of an outside group picks the constant 0x00 for all four bytes (+0.0, +0.0).  No select,
+      // no address arithmetic per load; the taps of an output are added in the order they always had, zero taps included.
+      // Rows: hh = h0 - 3 + r is block-uniform.  A row outside [0, H) is never loaded (no clamped address is formed): its half
+      // of the pair is the constant zero.  Blocks whose 18 halo rows are all inside (19 of 21 tile rows at H = 252) run the
+      // pipeline with no row test at all; the top / bottom blocks test each row with a scalar branch.
+      // Addresses: a load reads element  b H W C + hh W C + col C + c  with 0 <= hh <= H - 1 (tested, or implied by rows_in),
+      // 0 <= c <= C - 1 and col one of: w0 - 3 + q >= 0 (q < 3, w0 >= 4) or q (w0 == 0); w0 + q - 3 in [w0, w0 + 3], w0 <= W - 4;
+      // w0 + q - 3 <= W - 2 (q >= 7, w0 <= W - 8) or W - 10 + q <= W - 1 (w0 == W - 4).  So 0 <= col <= W - 1 and the element
+      // lies in [b H W C, (b + 1) H W C): inside clip b of x for every tile, the first rows of clip 0 and the last of clip
+      // B - 1 included (tests/test_cpu_dwconv_offsets.py mirrors this arithmetic for every tile).
+      const bool left = (w0 == 0), right = (w0 + 7 > W);
+      // (byte offsets, 32 bits: `scalar row base + zero-extended register + immediate` is one addressing mode of global_load)
+      const unsigned oL = 2u * (unsigned)((left ? 0 : w0 - 3) * C + c), oM = 2u * (unsigned)(w0 * C + c);
+      const unsigned oR = 2u * (unsigned)((right ? w0 + 1 : w0 + 4) * C + c);
+      constexpr unsigned SEL_PAIR = 0x05040100u, SEL_ZERO = 0x0c0c0c0cu;   // v_perm: (lo16 of row r, lo16 of row r + 1) / four zero bytes
+      const unsigned selL = left ? SEL_ZERO : SEL_PAIR, selR = right ? SEL_ZERO : SEL_PAIR;
+      const char* xc = (const char*)(x + (size_t)b * H * W * C);   // clip b (block-uniform)
+      const bool rows_in = (h0 >= 3) && (h0 + TH + 3 <= H);
+      // bit r: halo row r lies in the map, 0 <= h0 - 3 + r <= H - 1 (one independent scalar bit test per row: range compares of
+      // consecutive rows imply each other, and the compiler then clones the whole pipeline once per implication)
+      const unsigned rows = ((1u << min(TH + 6, H + 3 - h0)) - 1u) & ~((1u << max(0, 3 - h0)) - 1u);
+      auto conv = [&](auto check_rows) {
+        constexpr bool CHECK = decltype(check_rows)::value;
+        auto load_row = [&](int r, unsigned (&v)[10]) {   // halo row r -> the low halves of v, or zeros for a row outside the map
+          const int hh = h0 - 3 + r;
+          if (!CHECK || ((rows >> r) & 1u)) {
+            const char* xr = xc + (size_t)hh * W * C * 2;
 #pragma unroll
-        for (int q = 0; q < 10; ++q) p[q] = cn_h2{x0[q * C], x1[q * C]};
+            for (int q = 0; q < 10; ++q)
+              v[q] = *(const unsigned short*)(q < 3 ? xr + (size_t)oL + q * C * 2 : q < 7 ? xr + (size_t)oM + (q - 3) * C * 2 : xr + (size_t)oR + (q - 7) * C * 2);
+          } else {
+#pragma unroll
+            for (int q = 0; q < 10; ++q) v[q] = 0u;
+          }
+        };
+        auto pack = [&](const unsigned (&v0)[10], const unsigned (&v1)[10], cn_h2 (&p)[10]) {
+#pragma unroll
+          for (int q = 0; q < 10; ++q)
+            p[q] = __builtin_bit_cast(cn_h2, __builtin_amdgcn_perm(v1[q], v0[q], q < 3 ? selL : q < 7 ? SEL_PAIR : selR));
+        };
+        // With the row tests the pipeline is a chain of small basic blocks, and the compiler then sinks every product below the
+        // last load (all 180 loads in flight, 248 VGPRs).  An empty asm per accumulator after each pair keeps the products where
+        // they are written; it emits no instruction.  The version without row tests is one basic block and needs none.
+        // (The compiler's wait-counter analysis joins the paths of a loaded and a skipped row conservatively, so a top / bottom
+        // block waits for the loads of pair u + 1 before the products of pair u: 2 of 21 / 2 of 11 tile rows at 10 s.)
+        auto pin = [&]() {
+          if constexpr (CHECK) cn_dw_pin(acc, std::make_index_sequence<TH * 4>{});
+        };
+        unsigned a0[10], a1[10], b0[10], b1[10];
+        cn_h2 p[10];
+        load_row(0, a0);
+        load_row(1, a1);
+        // two-pair software pipeline: the loads of pair u + 1 are in flight under the products of pair u.  (Unrolled by template: the
+        // body is beyond the size up to which `#pragma unroll` unrolls, and a rolled loop would index the registers at run time.)
+        cn_static_for(std::make_integer_sequence<int, (NPR + 1) / 2>{}, [&](auto k) {
+          constexpr int u = 2 * decltype(k)::value;
+          if (u + 1 < NPR) {
+            load_row(2 * u + 2, b0);
+            load_row(2 * u + 3, b1);
+          }
+          pack(a0, a1, p);
+          fma_pair(2 * u, p);
+          pin();
+          if (u + 2 < NPR) {
+            load_row(2 * u + 4, a0);
+            load_row(2 * u + 5, a1);
+          }
+          if (u + 1 < NPR) {
+            pack(b0, b1, p);
+            fma_pair(2 * (u + 1), p);
+            pin();
+          }
+        });
       };
-      cn_h2 pa[10], pb[10];
-      load_pair(0, pa);
-#pragma unroll
-      for (int u = 0; u < NPR; u += 2) {   // two-pair software pipeline: the loads of pair u + 1 are in flight under the products of pair u
-        if (u + 1 < NPR) load_pair(2 * (u + 1), pb);
-        fma_pair(2 * u, pa);
-        if (u + 2 < NPR) load_pair(2 * (u + 2), pa);
-        if (u + 1 < NPR) fma_pair(2 * (u + 1), pb);
-      }
+      if (rows_in) conv(std::false_type{});
+      else conv(std::true_type{});
     } else {
+      // clamped address + zero-masked value for every thread: any W (maps narrower than the halo, W not a multiple of the tile)
 #pragma unroll
       for (int u = 0; u < NPR; ++u) {
         const int hh0 = h0 - 3 + 2 * u, hh1 = hh0 + 1;
@@ -430,13 +513,13 @@ extern "C" int conette_debug_dwprof(unsigned long long* out8, int reset) {
   return CN_OK;
 }
 
-template <typename T, typename XT, int C, int S, int TH>
-static int launch_dwconv(const XT* x, int B, int H, int W, const CnBlockW& bw, T* y, hipStream_t s) {
+template <typename T, typename XT, int C, int S, int TH, bool CLAMPED>
+static int launch_dwconv_as(const XT* x, int B, int H, int W, const CnBlockW& bw, T* y, hipStream_t s) {
   const int tiles_h = cn_cdiv(H, TH), tiles_w = cn_cdiv(W, 4 * S);
   constexpr int NPOS_ = TH * 4 * S, NT_ = (C > 384 ? 384 : C) * S;
   const size_t smem = ((size_t)NPOS_ * DwTile<C, S, TH>::PITCH + NPOS_ * (NT_ / NPOS_) + 2 * NPOS_) * sizeof(float);
-  CN_TRY(cn_configure_lds((const void*)cn_dwconv_ln_kernel<T, XT, C, S, TH>, (int)smem));
-  hipLaunchKernelGGL((cn_dwconv_ln_kernel<T, XT, C, S, TH>), dim3((unsigned)(B * tiles_h * tiles_w)),
+  CN_TRY(cn_configure_lds((const void*)cn_dwconv_ln_kernel<T, XT, C, S, TH, CLAMPED>, (int)smem));
+  hipLaunchKernelGGL((cn_dwconv_ln_kernel<T, XT, C, S, TH, CLAMPED>), dim3((unsigned)(B * tiles_h * tiles_w)),
                      dim3((C > 384 ? 384 : C) * S), smem, s, x, H, W, tiles_h, tiles_w, bw.dw_w, bw.dw_wp, bw.dw_b, bw.ln_w, bw.ln_b, y,
 #ifdef CN_G2_PROF
                      getenv("CN_DW_DEBUG") ? atoi(getenv("CN_DW_DEBUG")) : 0);
@@ -445,6 +528,19 @@ static int launch_dwconv(const XT* x, int B, int H, int W, const CnBlockW& bw, T
 #endif
   CN_LAUNCH_CHECK();
   return CN_OK;
+}
+
+// fp16 stream: the one-body kernel needs whole tiles across the width and a map wider than the halo (W = 56 / 28 of stages 0 / 1:
+// see the kernel); any other W -- none occurs in this model -- runs the clamped / masked body, which is correct for every W.
+template <typename T, typename XT, int C, int S, int TH>
+static int launch_dwconv(const XT* x, int B, int H, int W, const CnBlockW& bw, T* y, hipStream_t s) {
+  if constexpr (sizeof(XT) == 2) {
+    if constexpr (C <= 192)
+      if (W % (4 * S) == 0 && W >= 12) return launch_dwconv_as<T, XT, C, S, TH, false>(x, B, H, W, bw, y, s);
+    return launch_dwconv_as<T, XT, C, S, TH, true>(x, B, H, W, bw, y, s);
+  } else {
+    return launch_dwconv_as<T, XT, C, S, TH, false>(x, B, H, W, bw, y, s);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

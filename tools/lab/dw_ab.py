@@ -1,7 +1,7 @@
 """Same-box A/B of library builds for an encoder kernel class: per build (a child process each) the class time of one encode at
 B = 64 (HIP events around every launch of the class), the encoder-alone time per pass, and a hash of the frame embeddings.
-    python tools/lab/dw_ab.py libA.so libB.so ... [--cls dwconv_ln] [--prec bf16]
-(libraries are looked up in tools/lab/; the in-tree library is restored afterwards)"""
+    python tools/lab/dw_ab.py libA.so libB.so ... [--cls=dwconv_ln] [--prec=bf16] [--samples=320000] [--rounds=2]
+(libraries are looked up in tools/lab/; the in-tree library is restored afterwards; the first child that fails ends the run)"""
 import hashlib, os, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 LIB = os.path.join(ROOT, "conette-audio-captioning_amd", "libconette_hip.so")
@@ -11,14 +11,14 @@ import sys, os, hashlib, numpy as np, torch
 sys.path.insert(0, %r)
 import conette_amd
 from conette_amd import synth
-from conette_amd.engine import Engine
-cls, prec = sys.argv[1], sys.argv[2]
+from conette_amd.engine import Engine, encoder_geometry
+cls, prec, samples = sys.argv[1], sys.argv[2], int(sys.argv[3])
 sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in synth.synth_state_dict().items()}
 eng = Engine(sd, precision=prec)
 eng.set_encode_reserved_cus(24)
 B = 64
-wave = torch.from_numpy(synth.synth_waveforms(B, 320000, 1234)).cuda()
-fe = torch.empty((B, 31, 768), device="cuda"); clip = torch.empty((B, 527), device="cuda")
+wave = torch.from_numpy(synth.synth_waveforms(B, samples, 1234)).cuda()
+fe = torch.empty((B, encoder_geometry(samples)[1][3], 768), device="cuda"); clip = torch.empty((B, 527), device="cuda")
 for _ in range(5): eng.encode(wave, out=(fe, clip))
 torch.cuda.synchronize()
 h = hashlib.sha256(fe.cpu().numpy().tobytes()).hexdigest()[:16]
@@ -39,16 +39,19 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     cls = next((a.split("=")[1] for a in sys.argv if a.startswith("--cls=")), "dwconv_ln")
     prec = next((a.split("=")[1] for a in sys.argv if a.startswith("--prec=")), "bf16")
+    samples = next((a.split("=")[1] for a in sys.argv if a.startswith("--samples=")), "320000")
+    rounds = int(next((a.split("=")[1] for a in sys.argv if a.startswith("--rounds=")), "2"))
     keep = LIB + ".keep"
     shutil.copy(LIB, keep)
     try:
-        for rnd in range(2):
+        for rnd in range(rounds):
             for lib in args:
                 shutil.copy(os.path.join(ROOT, "tools", "lab", lib), LIB)
-                r = subprocess.run([sys.executable, "-c", CHILD, cls, prec], capture_output=True, text=True, timeout=600)
+                r = subprocess.run([sys.executable, "-c", CHILD, cls, prec, samples], capture_output=True, text=True, timeout=300)
                 print(f"{lib:28s}", (r.stdout.strip().splitlines() or ["(no output)"])[-1], flush=True)
-                if r.returncode != 0:
+                if r.returncode != 0:   # nothing more is started on a device that a child may have left in a bad state
                     print(r.stderr[-1500:], flush=True)
+                    sys.exit(1)
     finally:
         shutil.move(keep, LIB)
 
