@@ -168,6 +168,10 @@ __device__ __forceinline__ void cn_dw_pin1(float& v) { asm volatile("" : "+v"(v)
 template <int TH, size_t... I> __device__ __forceinline__ void cn_dw_pin(float (&acc)[TH][4], std::index_sequence<I...>) {
   (cn_dw_pin1(acc[I / 4][I % 4]), ...);
 }
+// The same for a per-thread address offset whose arithmetic the compiler could see through: behind the empty asm it stays one 32-bit
+// register beside a scalar base.  (Folded into `base + 2 c + constant`, every constant beyond the immediate becomes a 64-bit vector
+// address of its own: cn_fw_conv.)
+__device__ __forceinline__ void cn_dw_opaque(unsigned& v) { asm volatile("" : "+v"(v)); }
 
 template <typename T, typename XT, int C, int S, int TH, bool CLAMPED = false>
 __global__ __launch_bounds__((C > 384 ? 384 : C) * S) void cn_dwconv_ln_kernel(const XT* __restrict__ x, int H, int W, int tiles_h,
@@ -559,47 +563,57 @@ static int launch_dwconv(const XT* x, int B, int H, int W, const CnBlockW& bw, T
 // block has twice the waves over the same LDS tile (12 per CU instead of 6) and a thread half the accumulators; the taps of
 // an output are still added in the same (kh, kw) order, so the result does not depend on SPLIT.
 template <int C, int WW, int TH, int OW0, int NOW, typename XT>
-__device__ __forceinline__ void cn_fw_conv(const XT* __restrict__ xb /* + c */, int H, int h0,
-                                           const float* __restrict__ dw_w, const unsigned* __restrict__ dw_wp, float bias, int c,
-                                           float* __restrict__ s_v, int PITCH) {
+__device__ __forceinline__ void cn_fw_conv(const XT* __restrict__ xc /* clip b (block-uniform) */, int H, int h0,
+                                           const float* __restrict__ dw_w, const unsigned* __restrict__ dw_wp,
+                                           const float* __restrict__ dw_b, int c, float* __restrict__ s_v, int PITCH) {
   constexpr int Q0 = OW0 - 3 < 0 ? 0 : OW0 - 3, Q1 = OW0 + NOW + 3 > WW ? WW : OW0 + NOW + 3, NQ = Q1 - Q0;
   if constexpr (sizeof(XT) == 2) {
-    // fp16 stream: input rows in pairs, two taps per v_dot2_f32_f16 (see cn_dwconv_ln_kernel)
+    // fp16 stream: input rows in pairs, two taps per v_dot2_f32_f16, and the load pipeline of the one-body tiled kernel (see
+    // cn_dwconv_ln_kernel; profiles/dwconv_fw_notes.md).
+    // Addresses: a load reads element  b H WW C + hh WW C + col C + c  as `scalar row base + per-thread 32-bit byte offset +
+    // immediate`.  The row base  clip + hh WW C 2  bytes is block-uniform (clip, tile row and halo row are).  The 13-bit signed
+    // immediate holds q 2C bytes up to 4095, so the NQ columns Q0 .. Q1 - 1 go in groups of GRP with one per-thread offset each,
+    // computed once per thread: six + four columns at C = 384, 3 + 3 + 1 at C = 768.  Every column Q0 .. Q1 - 1 lies inside the
+    // map (taps outside it do not exist at compile time), so the pack needs no selector trick.
+    // Rows: hh = h0 - 3 + r.  A row outside [0, H) is never loaded (no address is formed for it): its half of the pair is the
+    // constant zero.  Blocks whose TH + 6 halo rows are all inside run the pipeline with no row test, in one basic block; the
+    // top / bottom blocks test each row with a scalar bit test.  So 0 <= hh <= H - 1, Q0 <= col <= Q1 - 1 <= WW - 1 and
+    // 0 <= c <= C - 1: the element lies in [b H WW C, (b + 1) H WW C), inside clip b for every tile, the first rows of clip 0
+    // and the last of clip B - 1 included (tests/test_cpu_dwconv_fw_offsets.py mirrors this arithmetic for every tile).
     static_assert(TH % 2 == 0, "row pairs");
+    constexpr int GRP = 4095 / (2 * C) + 1, NG = (NQ + GRP - 1) / GRP;   // columns per group (immediate <= 4095), groups
+    static_assert((GRP - 1) * C * 2 <= 4095, "a group's last column fits the immediate");
+    unsigned og[NG];   // byte offset of a group's first column from column 0 of a row
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      og[g] = 2u * (unsigned)((Q0 + g * GRP) * C + c);
+      cn_dw_opaque(og[g]);   // (else the groups are rebased on one 64-bit vector address per row and group)
+    }
+    constexpr unsigned SEL_PAIR = 0x05040100u;   // v_perm: (lo16 of row r, lo16 of row r + 1)
+    const char* xcb = (const char*)xc;
+    const bool rows_in = (h0 >= 3) && (h0 + TH + 3 <= H);
+    // bit r: halo row r lies in the map, 0 <= h0 - 3 + r <= H - 1 (one independent scalar bit test per row, as in the tiled kernel)
+    const unsigned rows = ((1u << min(TH + 6, H + 3 - h0)) - 1u) & ~((1u << max(0, 3 - h0)) - 1u);
     cn_h2 ke[3][7], ko[3][7];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        ke[a][j] = __builtin_bit_cast(cn_h2, dw_wp[(a * 7 + j) * C + c]);
-        ko[a][j] = __builtin_bit_cast(cn_h2, dw_wp[(21 + a * 7 + j) * C + c]);
-      }
     float acc[TH][NOW];
+    // Weights: `scalar base + per-thread 32-bit byte offset + immediate` too.  A base serves the WGRP taps whose rows its immediate
+    // reaches; behind the empty asm it stays a scalar pair (folded, every tap becomes a 64-bit vector address).
+    constexpr int WGRP = 4095 / (4 * C) + 1;
+    unsigned ow = 4u * (unsigned)c;
+    cn_dw_opaque(ow);
+    auto load_weights = [&]() {
 #pragma unroll
-    for (int a = 0; a < TH; ++a)
+      for (int t0 = 0; t0 < 42; t0 += WGRP) {
+        unsigned sb = (unsigned)(t0 * C * 4);
+        asm volatile("" : "+s"(sb));
+        const char* wb = (const char*)dw_wp + sb;
 #pragma unroll
-      for (int e = 0; e < NOW; ++e) acc[a][e] = bias;
-    auto load_pair = [&](int r, cn_h2 (&p)[NQ]) {   // halo rows r (even) and r + 1; rows above / below the map are zeros (block-uniform)
-      const int hh0 = h0 - 3 + r, hh1 = hh0 + 1;
-      XT v0[NQ], v1[NQ];
-      if (hh0 >= 0 && hh0 < H) {
-        const XT* xr = xb + (size_t)hh0 * WW * C;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) v0[q] = xr[(Q0 + q) * C];
-      } else {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) v0[q] = (XT)0.f;
+        for (int t = t0; t < t0 + WGRP && t < 42; ++t) {
+          const cn_h2 w = __builtin_bit_cast(cn_h2, *(const unsigned*)(wb + (size_t)ow + (t - t0) * C * 4));
+          if (t < 21) ke[t / 7][t % 7] = w;
+          else ko[(t - 21) / 7][t % 7] = w;
+        }
       }
-      if (hh1 >= 0 && hh1 < H) {
-        const XT* xr = xb + (size_t)hh1 * WW * C;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) v1[q] = xr[(Q0 + q) * C];
-      } else {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) v1[q] = (XT)0.f;
-      }
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) p[q] = cn_h2{v0[q], v1[q]};
     };
     auto fma_pair = [&](int r, const cn_h2 (&p)[NQ]) {
 #pragma unroll
@@ -621,21 +635,75 @@ __device__ __forceinline__ void cn_fw_conv(const XT* __restrict__ xb /* + c */, 
       }
     };
     constexpr int NPR = (TH + 6) / 2;
-    cn_h2 pa[NQ], pb[NQ];
-    load_pair(0, pa);
+    auto conv = [&](auto check_rows) {
+      constexpr bool CHECK = decltype(check_rows)::value;
+      auto load_row = [&](int r, unsigned (&v)[NQ]) {   // halo row r -> the low halves of v, or zeros for a row outside the map
+        const int hh = h0 - 3 + r;
+        if (!CHECK || ((rows >> r) & 1u)) {
+          const char* xr = xcb + (size_t)hh * WW * C * 2;
 #pragma unroll
-    for (int u = 0; u < NPR; u += 2) {
-      if (u + 1 < NPR) load_pair(2 * (u + 1), pb);
-      fma_pair(2 * u, pa);
-      if (u + 2 < NPR) load_pair(2 * (u + 2), pa);
-      if (u + 1 < NPR) fma_pair(2 * (u + 1), pb);
-    }
+          for (int q = 0; q < NQ; ++q) v[q] = *(const unsigned short*)(xr + (size_t)og[q / GRP] + (q % GRP) * C * 2);
+        } else {
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) v[q] = 0u;
+        }
+      };
+      auto pack = [&](const unsigned (&v0)[NQ], const unsigned (&v1)[NQ], cn_h2 (&p)[NQ]) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) p[q] = __builtin_bit_cast(cn_h2, __builtin_amdgcn_perm(v1[q], v0[q], SEL_PAIR));
+      };
+      // With the row tests the pipeline is a chain of small basic blocks and the compiler sinks the products below the last load;
+      // an empty asm per accumulator after each pair keeps them where they are written (it emits no instruction).  The copy without
+      // row tests is one basic block and needs none.
+      auto pin = [&]() {
+        if constexpr (CHECK) cn_static_for(std::make_integer_sequence<int, TH * NOW>{}, [&](auto i) { cn_dw_pin1(acc[decltype(i)::value / NOW][decltype(i)::value % NOW]); });
+      };
+      unsigned a0[NQ], a1[NQ], b0[NQ], b1[NQ];
+      cn_h2 p[NQ];
+      // the first row pair goes out before the bias and the 42 weight loads: one round trip covers all.  (The bias before the
+      // weights: behind them it would be the last load ahead of the tested rows 2 / 3, and the first product of the row-tested copy
+      // would wait for those rows too.)
+      load_row(0, a0);
+      load_row(1, a1);
+      const float bias = *(const float*)((const char*)dw_b + (size_t)ow);
+      load_weights();
+#pragma unroll
+      for (int a = 0; a < TH; ++a)
+#pragma unroll
+        for (int e = 0; e < NOW; ++e) acc[a][e] = bias;
+      // two-pair software pipeline: the raw halves of pair u + 1 are in flight under the products of pair u, a pair is packed only
+      // when its products are next (unrolled by template: a constant index in every step)
+      cn_static_for(std::make_integer_sequence<int, (NPR + 1) / 2>{}, [&](auto k) {
+        constexpr int u = 2 * decltype(k)::value;
+        if (u + 1 < NPR) {
+          load_row(2 * u + 2, b0);
+          load_row(2 * u + 3, b1);
+        }
+        pack(a0, a1, p);
+        fma_pair(2 * u, p);
+        pin();
+        if (u + 2 < NPR) {
+          load_row(2 * u + 4, a0);
+          load_row(2 * u + 5, a1);
+        }
+        if (u + 1 < NPR) {
+          pack(b0, b1, p);
+          fma_pair(2 * (u + 1), p);
+          pin();
+        }
+      });
+    };
+    // block-uniform: no wave executes both copies
+    if (rows_in) conv(std::false_type{});
+    else conv(std::true_type{});
 #pragma unroll
     for (int oh = 0; oh < TH; ++oh)
 #pragma unroll
       for (int ow = 0; ow < NOW; ++ow) s_v[(oh * WW + OW0 + ow) * PITCH + c] = acc[oh][ow];
     return;
   }
+  const XT* xb = xc + c;
+  const float bias = dw_b[c];
   float k[49];
 #pragma unroll
   for (int i = 0; i < 49; ++i) k[i] = dw_w[i * C + c];
@@ -706,13 +774,13 @@ __global__ __launch_bounds__(C* SPLIT > 384 ? 768 : 384) void cn_dwconv_ln_fw_ke
 
   if constexpr (SPLIT == 1) {
 #pragma unroll 1
-    for (int c = tid; c < C; c += CT) cn_fw_conv<C, WW, TH, 0, WW, XT>(xb0 + c, H, h0, dw_w, dw_wp, dw_b[c], c, s_v, PITCH);
+    for (int c = tid; c < C; c += CT) cn_fw_conv<C, WW, TH, 0, WW, XT>(xb0, H, h0, dw_w, dw_wp, dw_b, c, s_v, PITCH);
   } else {
     const int c = tid < C ? tid : tid - C;  // waves 0-5: left half, waves 6-11: right half (wave-uniform)
     if (tid < C)
-      cn_fw_conv<C, WW, TH, 0, WW / 2, XT>(xb0 + c, H, h0, dw_w, dw_wp, dw_b[c], c, s_v, PITCH);
+      cn_fw_conv<C, WW, TH, 0, WW / 2, XT>(xb0, H, h0, dw_w, dw_wp, dw_b, c, s_v, PITCH);
     else
-      cn_fw_conv<C, WW, TH, WW / 2, WW / 2, XT>(xb0 + c, H, h0, dw_w, dw_wp, dw_b[c], c, s_v, PITCH);
+      cn_fw_conv<C, WW, TH, WW / 2, WW / 2, XT>(xb0, H, h0, dw_w, dw_wp, dw_b, c, s_v, PITCH);
   }
   __syncthreads();
   // LayerNorm statistics: wave per position, C / 64 values per lane, two positions per iteration
