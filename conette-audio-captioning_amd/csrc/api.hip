@@ -14,6 +14,7 @@
 #include "mlp_rs16.h"
 #include "mlp_sp.h"
 #include "down_fused.h"
+#include "dec_consensus.h"
 
 static thread_local char g_err[512] = "";
 
@@ -742,6 +743,58 @@ extern "C" int conette_resample(const float* in, int32_t rows, int32_t n_in, int
   const int n_out = conette_resample_len(n_in, orig_sr, new_sr);
   hipLaunchKernelGGL(cn_resample_kernel, dim3((unsigned)((n_out + 255) / 256), (unsigned)rows), dim3(256), 0,
                      (hipStream_t)stream, in, n_in, n_out, t.o, t.n, t.width, t.K, t.dev, out);
+  CN_LAUNCH_CHECK();
+  return CN_OK;
+}
+
+// ---- consensus choice among candidate captions (dec_consensus.h): no context, no workspace, one launch
+extern "C" int conette_consensus(const int32_t* preds, const int32_t* lens, const float* weights, int32_t batch, int32_t n_cands,
+                                 int32_t row_len, int32_t utility, int32_t max_order, int32_t eos_id, int32_t pad_id,
+                                 float* expected, int32_t* best, float* margin, float* pairwise, void* stream) {
+  const char* bad = !preds ? "preds" : !expected ? "expected" : !best ? "best" : !margin ? "margin" : nullptr;
+  if (bad) {
+    cn_set_error("consensus: %s is NULL", bad);
+    return CN_ERR_ARG;
+  }
+  if (batch < 1) {
+    cn_set_error("consensus: batch=%d (expected at least 1)", batch);
+    return CN_ERR_ARG;
+  }
+  if (n_cands < 1 || n_cands > CONETTE_MAX_CANDS) {
+    cn_set_error("consensus: n_cands=%d unsupported (1..%d)", n_cands, CONETTE_MAX_CANDS);
+    return CN_ERR_ARG;
+  }
+  if (row_len < 1 || row_len > CN_CS_MAX_LEN) {
+    cn_set_error("consensus: row_len=%d unsupported (1..%d)", row_len, CN_CS_MAX_LEN);
+    return CN_ERR_ARG;
+  }
+  if (utility != CONETTE_UTILITY_NGRAM && utility != CONETTE_UTILITY_EDIT) {
+    cn_set_error("consensus: utility=%d unknown (CONETTE_UTILITY_NGRAM, CONETTE_UTILITY_EDIT)", utility);
+    return CN_ERR_ARG;
+  }
+  if (max_order < 1 || max_order > 4) {
+    cn_set_error("consensus: max_order=%d unsupported (1..4)", max_order);
+    return CN_ERR_ARG;
+  }
+  static_assert(CONETTE_MAX_CANDS == CN_CS_MAX_CANDS, "the kernel's tables are sized for CONETTE_MAX_CANDS candidates");
+  CnConsensusArgs a;
+  a.preds = preds;
+  a.lens = lens;
+  a.weights = weights;
+  a.uniform_w = 1.0f / (float)n_cands;
+  a.n = n_cands;
+  a.l = row_len;
+  a.utility = utility;
+  a.max_order = max_order;
+  a.eos_id = eos_id;
+  a.pad_id = pad_id;
+  a.expected = expected;
+  a.best = best;
+  a.margin = margin;
+  a.pairwise = pairwise;
+  const int npairs = n_cands * (n_cands - 1) / 2;   // a wave per pair at a time, and at least a thread per candidate
+  const int waves = std::min(CN_CS_MAX_WAVES, std::max(npairs, 1));
+  hipLaunchKernelGGL(cn_consensus_kernel, dim3((unsigned)batch), dim3((unsigned)waves * 64), 0, (hipStream_t)stream, a);
   CN_LAUNCH_CHECK();
   return CN_OK;
 }

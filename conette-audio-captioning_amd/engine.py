@@ -36,7 +36,7 @@ EXPORTS = (
     "conette_align_workspace_bytes", "conette_align", "conette_decode_groups_workspace_bytes", "conette_decode_groups",
     "conette_decode_constrained_workspace_bytes", "conette_decode_constrained",
     "conette_decode_required_workspace_bytes", "conette_decode_required",
-    "conette_decode_ensemble_workspace_bytes", "conette_decode_ensemble",
+    "conette_decode_ensemble_workspace_bytes", "conette_decode_ensemble", "conette_consensus",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -211,6 +211,9 @@ def load_library() -> C.CDLL:
     lib.conette_resample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.conette_resample_len.restype = C.c_int32
     lib.conette_resample_len.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_consensus.restype = C.c_int
+    lib.conette_consensus.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if lib.conette_abi_version() != 3:
         raise RuntimeError("libconette_hip.so ABI version mismatch")
     _lib = lib
@@ -1089,6 +1092,42 @@ class Engine:
         if self._ctx_dec is not self._ctx:
             _check(self.lib.conette_profile_read(self._ctx_dec, ms, cnt), "profile_read")
         return {PROF_CLASSES[i]: (float(ms[i]), int(cnt[i])) for i in range(n) if cnt[i] > 0}
+
+    def consensus(self, preds: torch.Tensor, lens: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                  utility: str = "ngram", max_order: int = 4, pairwise: bool = False) -> Dict[str, torch.Tensor]:
+        """The consensus (minimum-Bayes-risk) choice among the candidates of every clip (conette_consensus, include/conette_hip.h;
+        the rule: consensus.py): {"expected": (B, N) fp32, the weighted mean utility of each candidate against all of them,
+        "best": (B,) int32, "margin": (B,) fp32 [, "pairwise": (B, N, N) fp32] [, "weights": (B, N) fp32, the normalised weights
+        as the kernel read them, when ``weights`` are given]}.  ``preds`` (B, N, L) int32 or int64 (converted on
+        the device), ``lens`` (B, N) as ``sample`` reports them or None (contents end at the first <eos> / pad), ``weights`` (B, N)
+        finite and > 0 (normalised here, on the device) or None (equal).  Device tensors in, device tensors out, no host sync:
+        what only the values could show -- a length outside 0 .. L (clamped), a weight that is not positive -- is the caller's
+        contract (consensus.check_arguments states it)."""
+        from . import consensus as rule
+        if preds.ndim != 3:
+            raise ValueError(f"consensus: preds of shape {tuple(preds.shape)} (expected (batch, n_cands, row_len))")
+        b, n, l = (int(v) for v in preds.shape)
+        rule.check_arguments(preds, None, None, utility, max_order)     # (shapes and settings: nothing here reads device memory)
+        for name, t in (("lens", lens), ("weights", weights)):
+            if t is not None and tuple(t.shape) != (b, n):
+                raise ValueError(f"consensus: {name} of shape {tuple(t.shape)} for preds of shape {(b, n, l)}")
+        ids = preds.to(self.device, torch.int32).contiguous()
+        ln = None if lens is None else lens.to(self.device, torch.int32).contiguous()
+        w = None
+        if weights is not None:
+            w64 = weights.to(self.device, torch.float64)
+            w = (w64 / w64.sum(dim=1, keepdim=True)).to(torch.float32).contiguous()
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        out = {"expected": e((b, n), torch.float32), "best": e((b,), torch.int32), "margin": e((b,), torch.float32)}
+        if pairwise:
+            out["pairwise"] = e((b, n, n), torch.float32)
+        if w is not None:
+            out["weights"] = w
+        st = self.lib.conette_consensus(_ptr(ids), _ptr(ln), _ptr(w), b, n, l, rule.UTILITY[utility], int(max_order), self.eos_id,
+                                        self.pad_id, _ptr(out["expected"]), _ptr(out["best"]), _ptr(out["margin"]),
+                                        _ptr(out.get("pairwise")), _stream())
+        _check(st, "conette_consensus")
+        return out
 
     # ---- a1 --------------------------------------------------------------------------------
     def resample(self, x: torch.Tensor, orig_sr: int, new_sr: int) -> torch.Tensor:

@@ -11,6 +11,7 @@ from __future__ import annotations
 import csv
 import json
 import logging
+import math
 import os
 import os.path as osp
 from pathlib import Path
@@ -397,7 +398,8 @@ class CoNeTTEModel:
     def sample(self, x, num_samples: int = 1, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                seed: Optional[int] = None, generator: Optional[torch.Generator] = None, sr=None, x_shapes=None,
                preprocess: bool = True, task: Union[str, List[str], None] = None, min_pred_size: Optional[int] = None,
-               max_pred_size: Optional[int] = None, forbid_rep_mode: Optional[str] = None) -> Dict[str, Any]:
+               max_pred_size: Optional[int] = None, forbid_rep_mode: Optional[str] = None,
+               _consensus: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """``num_samples`` captions per clip DRAWN from the model's distribution (temperature, top-k and nucleus sampling on the
         device: conette_sample; the rule: sampling.py) instead of searched for.  ``x``, ``task`` and the size / mask arguments as
         in ``forward``, whose keys it returns: "mult_preds" (B, n, pred_size), "mult_cands", "mult_lprobs" (B, n) -- the mean
@@ -438,22 +440,118 @@ class CoNeTTEModel:
             res = self.engine.sample(audio, audio_shape[:, 1].to(torch.int32), self.batch_to_task_token_ids(dataset_lst, source_lst),
                                      self.get_forbid_rep_mask(forbid_rep_mode), n, min_pred, max_pred, temperature=temperature,
                                      top_k=top_k, top_p=top_p, generator=generator)
+            pick = None if _consensus is None else self._consensus_pick(res["preds"], res["lens"], res["sum_lprobs"], **_consensus)
             lens = res["lens"]
             mult_lprobs = res["sum_lprobs"] / lens.to(torch.float32)
-            best = mult_lprobs.argmax(dim=1)                                        # (the first maximum, like beam.py:214-217)
+            # (the first maximum, like beam.py:214-217 -- or the consensus pick)
+            best = mult_lprobs.argmax(dim=1) if pick is None else pick["best"].to(torch.long)
             rows = torch.arange(bsize, device=best.device)
-            pred_size, best_maxlen = (int(v) for v in torch.stack([res["sizes"][0], lens[rows, best].max()]).tolist())  # the one host sync
+            sizes = torch.stack([res["sizes"][0], lens[rows, best].max()])
+            if pick is None:
+                pred_size, best_maxlen = (int(v) for v in sizes.tolist())  # the one host sync
+            else:       # (the chosen indices come over with the sizes)
+                pred_size, best_maxlen, *index = (int(v) for v in torch.cat([sizes.to(torch.long), best]).tolist())
             mult_preds = res["preds"][:, :, :pred_size].to(torch.long).contiguous()
             preds = mult_preds[rows, best][:, :best_maxlen].contiguous()
+            mult_cands = self.tokenizer.decode_rec(mult_preds)
             outs = {
-                "cands": self.tokenizer.decode_rec(preds), "preds": preds, "lprobs": mult_lprobs[rows, best],
-                "mult_cands": self.tokenizer.decode_rec(mult_preds), "mult_preds": mult_preds, "mult_lprobs": mult_lprobs,
+                "cands": self.tokenizer.decode_rec(preds) if pick is None else [mult_cands[i][j] for i, j in enumerate(index)],
+                "preds": preds, "lprobs": mult_lprobs[rows, best],
+                "mult_cands": mult_cands, "mult_preds": mult_preds, "mult_lprobs": mult_lprobs,
                 "sum_lprobs": res["sum_lprobs"], "lens": lens, "tasks": tasks,
             }
             if clip_probs is not None:
                 outs["tags_probs"] = clip_probs
                 outs["tags"] = probs_to_names(clip_probs, 0.3, self.audioset_idx_to_name)
+            if pick is not None:
+                outs.update(self._consensus_keys(pick))
             return outs
+
+    # ---- consensus (minimum-Bayes-risk) choice among candidates: conette_consensus; the rule: consensus.py ---------------------
+    def _consensus_pick(self, mult_preds: Tensor, lens: Optional[Tensor], sum_lprobs: Optional[Tensor], utility: str = "ngram",
+                        max_order: int = 4, evidence: str = "uniform", evidence_scale: float = 1.0,
+                        mult_lprobs: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """Engine.consensus on a table of candidates, with the evidence weights computed on the device; no host sync."""
+        if evidence not in ("uniform", "model"):
+            raise ValueError(f"Invalid argument evidence={evidence!r}. (expected 'uniform' or 'model')")
+        if not math.isfinite(float(evidence_scale)):
+            raise ValueError(f"Invalid argument evidence_scale={evidence_scale}. (expected a finite number)")
+        weights = None
+        if evidence == "model":
+            if sum_lprobs is None:      # a search reports sum / length: the length is the tokens up to and including <eos>
+                ids = mult_preds
+                width = ids.shape[-1]
+                pos = torch.arange(width, device=ids.device).expand_as(ids)
+                length = torch.where(ids == self.engine.eos_id, pos + 1, width).amin(dim=-1)
+                total = mult_lprobs.to(torch.float64) * length.to(torch.float64)
+                total = torch.where(torch.isfinite(mult_lprobs), total, mult_lprobs.to(torch.float64))   # (a void slot: -inf, weight 0)
+            else:
+                total = sum_lprobs.to(torch.float64)
+            weights = torch.softmax(float(evidence_scale) * total, dim=1)
+        return self.engine.consensus(mult_preds, lens, weights, utility=utility, max_order=max_order)
+
+    @staticmethod
+    def _consensus_keys(pick: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        keys = {"consensus": pick["expected"], "consensus_index": pick["best"].to(torch.long), "consensus_margin": pick["margin"]}
+        if "weights" in pick:
+            keys["consensus_weights"] = pick["weights"]
+        return keys
+
+    @torch.no_grad()
+    def select_consensus(self, outputs: Dict[str, Any], utility: str = "ngram", max_order: int = 4, evidence: str = "uniform",
+                         evidence_scale: float = 1.0) -> Dict[str, Any]:
+        """ONE caption per clip out of the candidates a call returned: the consensus (minimum-Bayes-risk) choice, the candidate
+        that agrees most with all the others (conette_consensus on the device; the rule: consensus.py).  ``outputs`` is the dict
+        of ``forward`` / ``sample`` / ``caption_diverse`` / ``caption_constrained`` / ``caption_ensemble``: its "mult_preds" are
+        the candidates, cut by "lens" where present (``sample``) and at the first <eos> or pad otherwise.  ``utility`` "ngram"
+        (mean n-gram F-score over the orders 1 .. ``max_order`` <= 4) or "edit" (1 - token edit distance / longer length);
+        ``evidence`` "uniform" weights the candidates equally, "model" by softmax_j(``evidence_scale`` * sum of the caption's
+        token log-probabilities) ("sum_lprobs" where present, else "mult_lprobs" times the caption's length), computed on the
+        device; a void slot of a steered search (score -inf) weighs nothing.  Returns the same dict with "cands" / "preds" /
+        "lprobs" replaced by the pick, plus "consensus" (B, N) -- every candidate's expected utility --, "consensus_index" (B,),
+        "consensus_margin" (B,) and, under "model", "consensus_weights" (B, N).  At most 64 candidates of at most 64 tokens.
+        Reads the B chosen indices back to pick the strings: its one host sync."""
+        if "mult_preds" not in outputs:
+            raise ValueError("select_consensus: outputs hold no 'mult_preds' (expected the dict of forward / sample / caption_*)")
+        with torch.cuda.device(self.device):
+            mult_preds = outputs["mult_preds"]
+            lens = outputs.get("lens")
+            pick = self._consensus_pick(mult_preds, lens, outputs.get("sum_lprobs"), utility=utility, max_order=max_order,
+                                        evidence=evidence, evidence_scale=evidence_scale, mult_lprobs=outputs["mult_lprobs"])
+            best = pick["best"].to(torch.long)
+            bsize, _, width = mult_preds.shape
+            rows = torch.arange(bsize, device=best.device)
+            chosen = mult_preds[rows, best]
+            if lens is not None:
+                length = lens[rows, best].to(torch.long)
+            else:
+                pos = torch.arange(width, device=best.device).expand_as(chosen)
+                length = torch.where(chosen == self.engine.eos_id, pos + 1, width).amin(dim=-1)
+            best_maxlen, *index = (int(v) for v in torch.cat([length.max().reshape(1), best]).tolist())   # the one host sync
+            outs = dict(outputs)
+            outs["preds"] = chosen[:, :best_maxlen].to(torch.long).contiguous()
+            outs["cands"] = [outputs["mult_cands"][i][j] for i, j in enumerate(index)]
+            outs["lprobs"] = outputs["mult_lprobs"][rows, best]
+            outs.update(self._consensus_keys(pick))
+            return outs
+
+    @torch.no_grad()
+    def caption_consensus(self, x, num_samples: int = 16, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                          seed: Optional[int] = None, generator: Optional[torch.Generator] = None, sr=None, x_shapes=None,
+                          preprocess: bool = True, task: Union[str, List[str], None] = None, min_pred_size: Optional[int] = None,
+                          max_pred_size: Optional[int] = None, forbid_rep_mode: Optional[str] = None, utility: str = "ngram",
+                          max_order: int = 4, evidence: str = "uniform", evidence_scale: float = 1.0) -> Dict[str, Any]:
+        """Sample-and-rerank: ``sample(x, num_samples, ...)`` followed by ``select_consensus`` on its draws, with the choice made
+        on the device in between -- the chosen indices come to the host with the sizes, in ``sample``'s one host sync.  Returns
+        exactly ``select_consensus(sample(...))``: "cands" / "preds" / "lprobs" are the consensus caption of each clip, the
+        "mult_*" keys all the draws.  ``num_samples`` <= 64."""
+        from . import consensus
+        if not 1 <= int(num_samples) <= consensus.MAX_CANDS:       # (before anything is drawn)
+            raise ValueError(f"Invalid argument num_samples={num_samples}: n_cands unsupported (1..{consensus.MAX_CANDS})")
+        return self.sample(x, num_samples=num_samples, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                           generator=generator, sr=sr, x_shapes=x_shapes, preprocess=preprocess, task=task,
+                           min_pred_size=min_pred_size, max_pred_size=max_pred_size, forbid_rep_mode=forbid_rep_mode,
+                           _consensus=dict(utility=utility, max_order=max_order, evidence=evidence, evidence_scale=evidence_scale))
 
     @torch.no_grad()
     def caption_diverse(self, x, num_groups: int = 3, group_beam_size: int = 1, diversity_penalty: float = 0.5, sr=None,

@@ -3,7 +3,7 @@
 
     python -m conette_amd.predict --audio a.wav b.wav --task clotho --model_name DIR_OR_HUB_NAME \
         [--csv_export out.csv] [--precision certified|certified:BASE|bf16|bf16+f16dec|f16|mixed|mixed16|exact|fp32]
-        [--sample N --temperature T --top_k K --top_p P --seed S] [--align]
+        [--sample N --temperature T --top_k K --top_p P --seed S [--consensus ngram|edit --consensus_order K]] [--align]
         [--beam_groups G --group_beam W --diversity_penalty L]
         [--prefix "a dog" --ban_words WORD ... --no_repeat_ngram N]
 
@@ -55,6 +55,11 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
     parser.add_argument("--temperature", type=float, help="With --sample: softmax temperature.", default=1.0)
     parser.add_argument("--top_k", type=int, help="With --sample: keep the k most likely tokens (0: off).", default=0)
     parser.add_argument("--top_p", type=float, help="With --sample: nucleus mass (1: off).", default=1.0)
+    parser.add_argument("--consensus", type=str, choices=("ngram", "edit"), default=None,
+                        help="With --sample: one row per file, the draw that agrees most with all the others (minimum Bayes risk; "
+                             "CoNeTTEModel.caption_consensus) by n-gram overlap or by token edit distance, instead of one row per draw.")
+    parser.add_argument("--consensus_order", type=int, default=None,
+                        help="With --consensus ngram: the longest n-gram counted, 1 .. 4 (default 4).")
     parser.add_argument("--align", action="store_true",
                         help="One row per word of each file's caption -- audio, task, word, start, end (seconds) -- instead of one per file: "
                              "where in the clip the decoder listens while it predicts the word (CoNeTTEModel.align_captions).")
@@ -90,6 +95,16 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
                         help="certified (default: fp16 pipeline + id certificate, uncertified clips re-run exactly), certified:<base>, "
                              "bf16, bf16+f16dec, f16, mixed, mixed16, exact, fp32")
     args = parser.parse_args(argv)
+    if args.consensus is None and args.consensus_order is not None:
+        raise ValueError("--consensus_order goes with --consensus")
+    if args.consensus is not None:
+        if args.sample <= 0:
+            raise ValueError("--consensus chooses among the draws of --sample N; it does not go without --sample")
+        if args.consensus_order is None:
+            args.consensus_order = 4
+        import numpy as np
+        from . import consensus
+        consensus.check_arguments(np.zeros((1, args.sample, 1), dtype=np.int32), None, None, args.consensus, args.consensus_order)
     if args.beam_groups > 0 and args.sample > 0:
         raise ValueError("--beam_groups searches for different captions; it does not go with --sample")
     if args.beam_groups > 0 and args.align:
@@ -262,6 +277,10 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         required = None if args.require_words is None else [w.split("|") for w in args.require_words]
         outs = model.caption_constrained(fpaths, prefix=args.prefix, banned=args.ban_words, no_repeat_ngram_size=args.no_repeat_ngram,
                                          task=tasks, required=required)
+        results = format_results(fpaths, outs["tasks"], outs["cands"])
+    elif args.sample > 0 and args.consensus is not None:   # N draws per file, one row: the consensus among them
+        outs = model.caption_consensus(fpaths, num_samples=args.sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                       seed=args.seed, task=tasks, utility=args.consensus, max_order=args.consensus_order)
         results = format_results(fpaths, outs["tasks"], outs["cands"])
     elif args.sample > 0:   # N draws per file, in the order drawn
         outs = model.sample(fpaths, num_samples=args.sample, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,

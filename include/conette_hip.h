@@ -430,6 +430,36 @@ int conette_decode_required(conette_ctx* ctx, const float* frame_embs, const int
                             int32_t* trace_sel, float* trace_val, float* step_logits, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* Consensus (minimum-Bayes-risk) choice among candidate captions: per clip the candidate that agrees most with all the others, each
+ * weighted by the evidence for it (csrc/dec_consensus.h; the CPU statement of the rule, its fp32 arithmetic included, is
+ * conette_amd/consensus.py).  Takes no context and no workspace: one launch, one workgroup per clip.
+ *   preds    : dev (B, n_cands, row_len) int32, any ids in 0 .. 2^31 - 1 (compared as whole words)
+ *   lens     : dev (B, n_cands) int32 or NULL.  Given (conette_sample's `lens`, <eos> included; clamped to 0 .. row_len): the content
+ *              of a candidate is row[:len] without its last token if that is eos_id.  NULL: the tokens in front of the first eos_id or
+ *              pad_id of the row, the whole row if neither occurs.  A content may be empty
+ *   weights  : dev (B, n_cands) fp32 or NULL -- finite, > 0, normalised to sum 1 per clip by the caller (used as given); NULL: every
+ *              weight is fp32(1) / fp32(n_cands)
+ *   utility  : CONETTE_UTILITY_NGRAM  u(i, j) = the mean over the orders n = 1 .. max_order that count of F_n = 2 m_n / (t_i + t_j),
+ *                                     t_i = max(|c_i| - n + 1, 0), m_n = the clipped n-gram match (sum over distinct n-grams of the
+ *                                     smaller count); an order with t_i + t_j = 0 does not count; u = 1 when none counts
+ *              CONETTE_UTILITY_EDIT   u(i, j) = 1 - levenshtein(c_i, c_j) / max(|c_i|, |c_j|) at unit costs; 1 when both are empty
+ *   max_order: 1 .. 4 (checked under either utility, read by CONETTE_UTILITY_NGRAM)
+ *   expected : dev (B, n_cands) fp32, E_i = sum_j w_j u(i, j), j = 0 .. n_cands - 1 in this order, i included
+ *   best     : dev (B) int32, the first index of the maximum E
+ *   margin   : dev (B) fp32, E[best] minus the largest E at any other index: +inf with one candidate, 0 when a duplicate ties
+ *   pairwise : dev (B, n_cands, n_cands) fp32 or NULL, u itself (symmetric, diagonal 1)
+ * Counts and distances are exact integers and every fp32 operation is rounded on its own in the order consensus.py fixes (one
+ * division per F_n, the orders added in ascending n, one division by their number; products w_j u(i, j) added from 0 in ascending j,
+ * no fused multiply-add): the results equal consensus.select_fp32 bit for bit.  1 <= n_cands <= CONETTE_MAX_CANDS, 1 <= row_len <= 64.
+ * A failing call names the argument and launches nothing.  Asynchronous on `stream`, allocates nothing, capturable; bit-identical from
+ * run to run. */
+#define CONETTE_UTILITY_NGRAM 0
+#define CONETTE_UTILITY_EDIT 1
+#define CONETTE_MAX_CANDS 64
+int conette_consensus(const int32_t* preds, const int32_t* lens, const float* weights, int32_t batch, int32_t n_cands,
+                      int32_t row_len, int32_t utility, int32_t max_order, int32_t eos_id, int32_t pad_id, float* expected,
+                      int32_t* best, float* margin, float* pairwise, void* stream);
+
 /* a1: torchaudio.functional.resample (preprocessor.py:134-141), sinc_interpolation width 6,
  * rolloff 0.99.  in: dev (rows, n_in) fp32; out: dev (rows, n_out), n_out = ceil(n_in*new/orig). */
 int conette_resample(const float* in, int32_t rows, int32_t n_in, int32_t orig_sr, int32_t new_sr, float* out,
