@@ -26,6 +26,7 @@ __device__ __forceinline__ void cn_watch_stat(float v) {
 #include "mlp_rs16.h"
 #include "mlp_sp.h"
 #include "down_fused.h"
+#include "enc_tags.h"
 
 // ---------------------------------------------------------------------------------------------
 // stem: Conv2d(1 -> 96, k 4x4, s 4x4, pad (4, 0)) + LayerNorm(channels_first, eps 1e-6)
@@ -1302,4 +1303,123 @@ extern "C" int conette_encode(conette_ctx* ctx, const float* wave, int32_t batch
     default:
       return encode_impl<float, float>(ctx, wave, batch, n_samples, frame_embs, clip_probs, taps, (char*)workspace, (hipStream_t)stream);
   }
+}
+
+// ---- tag timeline (enc_tags.h; the rule: conette_amd/tagging.py) ----------------------------------------------------------------
+// the workspace holds the GEMM's operand rows: (B, t_audio, 768) of the precision's operand type
+extern "C" size_t conette_tag_frames_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio) {
+  if (!ctx || batch < 0 || t_audio < 0) return 0;
+  return cn_align((size_t)batch * t_audio * CN_FEAT * ctx->esize);
+}
+
+template <typename T>
+static int tag_frames_impl(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, int B, int Tn, int window,
+                           float* frame_probs, T* z, hipStream_t s) {
+  const dim3 grid((unsigned)cn_cdiv(Tn, CN_TAG_TT), (unsigned)B);
+  hipLaunchKernelGGL((cn_window_pool_ln_kernel<T>), grid, dim3(256), 0, s, frame_embs, frame_lens, Tn, (window - 1) / 2, window / 2,
+                     ctx->norm_w, ctx->norm_b, z);
+  CN_LAUNCH_CHECK();
+  EpiBiasAct<float> eh{ctx->head_b, frame_probs, CN_N_TAGS, ACT_SIGMOID};
+  CN_TRY(cn_mm((const T*)z, CN_FEAT, (const T*)ctx->head_w, CN_FEAT, B * Tn, CN_N_TAGS, CN_FEAT, eh, s));
+  hipLaunchKernelGGL(cn_tag_zero_rows_kernel, grid, dim3(256), 0, s, frame_probs, frame_lens, Tn, CN_N_TAGS);
+  CN_LAUNCH_CHECK();
+  return CN_OK;
+}
+
+extern "C" int conette_tag_frames(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, int32_t batch,
+                                  int32_t t_audio, int32_t window, float* frame_probs, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  const char* bad = !ctx ? "ctx" : !frame_embs ? "frame_embs" : !frame_lens ? "frame_lens" : !frame_probs ? "frame_probs" : nullptr;
+  if (bad) {
+    cn_set_error("tag_frames: %s is NULL", bad);
+    return CN_ERR_ARG;
+  }
+  if (ctx->no_encoder) {
+    cn_set_error("tag_frames: decoder-only context (created without preprocessor.encoder.* tensors: it holds no clip head)");
+    return CN_ERR_ARG;
+  }
+  if (batch < 0 || batch > 65535) {
+    cn_set_error("tag_frames: batch=%d unsupported (0..65535)", batch);
+    return CN_ERR_ARG;
+  }
+  // (B t_audio 768 < 2^31: 31 days of audio)
+  if (t_audio < 0 || (int64_t)batch * t_audio > INT32_MAX / CN_FEAT) {
+    cn_set_error("tag_frames: t_audio=%d unsupported (0..%d frames in the whole batch)", t_audio, INT32_MAX / CN_FEAT);
+    return CN_ERR_ARG;
+  }
+  if (window < 1 || window > CONETTE_TAG_MAX_WINDOW) {
+    cn_set_error("tag_frames: window=%d unsupported (1..%d frames)", window, CONETTE_TAG_MAX_WINDOW);
+    return CN_ERR_ARG;
+  }
+  if (batch == 0 || t_audio == 0) return CN_OK;
+  const size_t need = conette_tag_frames_workspace_bytes(ctx, batch, t_audio);
+  if (!workspace) {
+    cn_set_error("tag_frames: workspace is NULL");
+    return CN_ERR_ARG;
+  }
+  if (workspace_bytes < need) {
+    cn_set_error("tag_frames: workspace_bytes %zu < %zu", workspace_bytes, need);
+    return CN_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  switch (ctx->cfg.precision) {
+    case CONETTE_PREC_BF16: return tag_frames_impl(ctx, frame_embs, frame_lens, batch, t_audio, window, frame_probs, (bf16_t*)workspace, s);
+    case CONETTE_PREC_F16: return tag_frames_impl(ctx, frame_embs, frame_lens, batch, t_audio, window, frame_probs, (half_t*)workspace, s);
+    case CONETTE_PREC_F16X2: return tag_frames_impl(ctx, frame_embs, frame_lens, batch, t_audio, window, frame_probs, (sp16_t*)workspace, s);
+    default: return tag_frames_impl(ctx, frame_embs, frame_lens, batch, t_audio, window, frame_probs, (float*)workspace, s);
+  }
+}
+
+extern "C" int conette_tag_events(const float* frame_probs, const int32_t* frame_lens, int32_t batch, int32_t t_audio,
+                                  int32_t n_tags, float on_threshold, float off_threshold, int32_t min_frames, int32_t max_gap,
+                                  int32_t max_events, int32_t* spans, float* peaks, int32_t* peak_frames, int32_t* counts,
+                                  void* stream) {
+  const char* bad = !frame_probs ? "frame_probs" : !frame_lens ? "frame_lens" : !spans ? "spans" : !peaks ? "peaks"
+                    : !peak_frames ? "peak_frames" : !counts ? "counts" : nullptr;
+  if (bad) {
+    cn_set_error("tag_events: %s is NULL", bad);
+    return CN_ERR_ARG;
+  }
+  if (batch < 0 || t_audio < 0 || n_tags < 0 || (int64_t)batch * n_tags > INT32_MAX / CONETTE_TAG_MAX_EVENTS) {
+    cn_set_error("tag_events: %s=%d unsupported (at least 0, batch * n_tags at most %d)", batch < 0 ? "batch" : t_audio < 0 ? "t_audio" : "n_tags",
+                 batch < 0 ? batch : t_audio < 0 ? t_audio : n_tags, INT32_MAX / CONETTE_TAG_MAX_EVENTS);
+    return CN_ERR_ARG;
+  }
+  if (!(on_threshold > 0.0f && on_threshold <= 1.0f)) {  // (a NaN fails both)
+    cn_set_error("tag_events: on_threshold=%g unsupported (finite, 0 < off_threshold <= on_threshold <= 1)", (double)on_threshold);
+    return CN_ERR_ARG;
+  }
+  if (!(off_threshold > 0.0f && off_threshold <= on_threshold)) {
+    cn_set_error("tag_events: off_threshold=%g unsupported (finite, 0 < off_threshold <= on_threshold = %g)", (double)off_threshold,
+                 (double)on_threshold);
+    return CN_ERR_ARG;
+  }
+  if (min_frames < 0 || max_gap < 0) {
+    cn_set_error("tag_events: %s=%d unsupported (at least 0)", min_frames < 0 ? "min_frames" : "max_gap", min_frames < 0 ? min_frames : max_gap);
+    return CN_ERR_ARG;
+  }
+  if (max_events < 1 || max_events > CONETTE_TAG_MAX_EVENTS) {
+    cn_set_error("tag_events: max_events=%d unsupported (1..%d)", max_events, CONETTE_TAG_MAX_EVENTS);
+    return CN_ERR_ARG;
+  }
+  const long n_seq = (long)batch * n_tags;
+  if (n_seq == 0) return CN_OK;
+  CnTagEventsArgs a;
+  a.probs = frame_probs;
+  a.lens = frame_lens;
+  a.batch = batch;
+  a.t_audio = t_audio;
+  a.n_tags = n_tags;
+  a.on = on_threshold;
+  a.off = off_threshold;
+  a.min_frames = min_frames;
+  a.max_gap = max_gap;
+  a.max_events = max_events;
+  a.spans = spans;
+  a.peaks = peaks;
+  a.peak_frames = peak_frames;
+  a.counts = counts;
+  hipLaunchKernelGGL(cn_tag_events_kernel, dim3((unsigned)((n_seq + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  CN_LAUNCH_CHECK();
+  return CN_OK;
 }

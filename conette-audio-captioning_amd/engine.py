@@ -37,6 +37,7 @@ EXPORTS = (
     "conette_decode_constrained_workspace_bytes", "conette_decode_constrained",
     "conette_decode_required_workspace_bytes", "conette_decode_required",
     "conette_decode_ensemble_workspace_bytes", "conette_decode_ensemble", "conette_consensus",
+    "conette_tag_frames_workspace_bytes", "conette_tag_frames", "conette_tag_events",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -214,6 +215,14 @@ def load_library() -> C.CDLL:
     lib.conette_consensus.restype = C.c_int
     lib.conette_consensus.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.conette_tag_frames_workspace_bytes.restype = C.c_size_t
+    lib.conette_tag_frames_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.conette_tag_frames.restype = C.c_int
+    lib.conette_tag_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]
+    lib.conette_tag_events.restype = C.c_int
+    lib.conette_tag_events.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if lib.conette_abi_version() != 3:
         raise RuntimeError("libconette_hip.so ABI version mismatch")
     _lib = lib
@@ -1127,6 +1136,52 @@ class Engine:
                                         self.pad_id, _ptr(out["expected"]), _ptr(out["best"]), _ptr(out["margin"]),
                                         _ptr(out.get("pairwise")), _stream())
         _check(st, "conette_consensus")
+        return out
+
+    # ---- tag timeline: conette_tag_frames / conette_tag_events; the rule: tagging.py ------------------------------------------------
+    def tag_frames(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, window: int) -> torch.Tensor:
+        """Per-frame AudioSet tag probabilities (conette_tag_frames, include/conette_hip.h): the clip head pooled over ``window``
+        frames around every frame.  frame_embs (B, T, 768), frame_lens (B,) -> (B, T, 527) fp32 on the device, rows at or beyond a
+        clip's length exact zeros.  Runs on the encoder's context (a certified engine: its 16-bit base); no host sync."""
+        from . import tagging
+        if frame_embs.ndim != 3 or frame_embs.shape[2] != FEAT:
+            raise ValueError(f"tag_frames: frame_embs of shape {tuple(frame_embs.shape)} (expected (batch, t_audio, {FEAT}))")
+        b, t = int(frame_embs.shape[0]), int(frame_embs.shape[1])
+        if tuple(frame_lens.shape) != (b,):
+            raise ValueError(f"tag_frames: frame_lens of shape {tuple(frame_lens.shape)} for frame_embs of shape {tuple(frame_embs.shape)}")
+        tagging.check_arguments(window=window)
+        fe = frame_embs.to(self.device, torch.float32).contiguous()
+        lens = frame_lens.to(self.device, torch.int32).contiguous()
+        probs = torch.empty((b, t, N_TAGS), dtype=torch.float32, device=self.device)
+        if probs.numel() == 0:
+            return probs
+        wsb = self._workspace("tags", max(1, int(self.lib.conette_tag_frames_workspace_bytes(self._ctx, b, t))))
+        st = self.lib.conette_tag_frames(self._ctx, _ptr(fe), _ptr(lens), b, t, int(window), _ptr(probs), _ptr(wsb), wsb.numel(), _stream())
+        _check(st, "conette_tag_frames")
+        return probs
+
+    def tag_events(self, frame_probs: torch.Tensor, frame_lens: torch.Tensor, on: float, off: Optional[float] = None,
+                   min_frames: int = 1, max_gap: int = 0, max_events: int = 16) -> Dict[str, torch.Tensor]:
+        """The events of every (clip, tag) sequence of ``frame_probs`` (B, T, n_tags) fp32 (conette_tag_events; the rule:
+        tagging.events): {"spans": (B, n_tags, max_events, 2) int32, "peaks": (B, n_tags, max_events) fp32, "peak_frames":
+        (B, n_tags, max_events) int32, "counts": (B, n_tags) int32} on the device; no host sync.  ``off`` None: off = on."""
+        from . import tagging
+        if frame_probs.ndim != 3:
+            raise ValueError(f"tag_events: frame_probs of shape {tuple(frame_probs.shape)} (expected (batch, t_audio, n_tags))")
+        b, t, c = (int(v) for v in frame_probs.shape)
+        if tuple(frame_lens.shape) != (b,):
+            raise ValueError(f"tag_events: frame_lens of shape {tuple(frame_lens.shape)} for frame_probs of shape {(b, t, c)}")
+        off = on if off is None else off
+        tagging.check_arguments(on=on, off=off, min_frames=min_frames, max_gap=max_gap, max_events=max_events)
+        p = frame_probs.to(self.device, torch.float32).contiguous()
+        lens = frame_lens.to(self.device, torch.int32).contiguous()
+        m = int(max_events)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        out = {"spans": e((b, c, m, 2), torch.int32), "peaks": e((b, c, m), torch.float32), "peak_frames": e((b, c, m), torch.int32),
+               "counts": e((b, c), torch.int32)}
+        st = self.lib.conette_tag_events(_ptr(p), _ptr(lens), b, t, c, float(on), float(off), int(min_frames), int(max_gap), m,
+                                         _ptr(out["spans"]), _ptr(out["peaks"]), _ptr(out["peak_frames"]), _ptr(out["counts"]), _stream())
+        _check(st, "conette_tag_events")
         return out
 
     # ---- a1 --------------------------------------------------------------------------------

@@ -913,6 +913,83 @@ class CoNeTTEModel:
                 outs["attn_layers"] = res["attn_layers"].reshape(-1, bsize, n_caps, size - 1, t)
             return outs
 
+    def _tag_indices(self, tags) -> Optional[set]:
+        """the indices a ``tags=`` filter of names or indices keeps (None: all)"""
+        if tags is None:
+            return None
+        by_name = {name: idx for idx, name in self.audioset_idx_to_name.items()}
+        wanted = set()
+        for tag in ([tags] if isinstance(tags, (str, int)) else tags):
+            if isinstance(tag, str):
+                if tag not in by_name:
+                    raise ValueError(f"Invalid argument tags: unknown AudioSet tag name {tag!r}.")
+                wanted.add(int(by_name[tag]))
+            elif isinstance(tag, bool) or int(tag) != tag or not 0 <= int(tag) < 527:
+                raise ValueError(f"Invalid argument tags: unknown AudioSet tag index {tag!r}. (expected 0..526 or a name)")
+            else:
+                wanted.add(int(tag))
+        return wanted
+
+    @torch.no_grad()
+    def tag_timeline(self, x, window_s: float = 2.24, threshold: float = 0.3, off_threshold: Optional[float] = None,
+                     min_duration_s: float = 0.0, max_gap_s: float = 0.0, max_events: int = 16, tags=None, sr=None, x_shapes=None,
+                     preprocess: bool = True) -> Dict[str, Any]:
+        """WHEN each AudioSet tag is heard in a clip -- sound event detection with the model as shipped, the tag-side counterpart
+        of ``align_captions``: the clip head (max + mean over time, LayerNorm, head_audioset, sigmoid) pooled over a window of
+        ``window_s`` seconds around every 0.32 s frame of the encoder instead of over the whole clip (conette_tag_frames), and the
+        frames of every tag gathered into events on the device (conette_tag_events; both rules: tagging.py).
+
+        ``x`` as in ``score_captions``.  A frame opens an event of a tag where its probability reaches ``threshold``; the event
+        extends over the neighbouring frames that stay at or above ``off_threshold`` (None: = ``threshold``, plain thresholding);
+        events of one tag at most ``max_gap_s`` apart are merged, then those shorter than ``min_duration_s`` are dropped (seconds,
+        rounded half up to frames).  Returns {"frame_probs": (B, T, 527) on the device, rows beyond a clip's frames zero,
+        "frame_lens": (B,), "frame_sec", "event_counts": (B, 527) -- the true numbers --, "events_truncated": (B,) bool, true where
+        a tag has more than the ``max_events`` (1 .. 64) events kept, "events": per clip a list of {"tag", "index", "onset",
+        "offset", "peak", "peak_time"} (seconds from the clip's start; "peak_time" is the centre of the strongest frame) sorted by
+        (onset, index) [, "tags_probs", "tags": ``forward``'s, when the call ran the preprocessor]}.  ``tags`` (names or indices)
+        filters the "events" list only: the device computes all 527.  The event tables come to the host in one transfer.
+        Precision "certified" runs on its 16-bit base context, like ``score_captions``."""
+        import numpy as np
+        from . import alignment, tagging
+        window, shortest, gap = tagging.window_frames(window_s), tagging.min_frames(min_duration_s), tagging.gap_frames(max_gap_s)
+        off = threshold if off_threshold is None else off_threshold
+        tagging.check_arguments(window=window, on=threshold, off=off, min_frames=shortest, max_gap=gap, max_events=max_events)
+        wanted = self._tag_indices(tags)
+        with torch.cuda.device(self.device):
+            keep: Dict[str, Any] = {}
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess, keep)
+            self._refuse_encoder_overflow(preprocess)
+            lens = torch.as_tensor(audio_shape)[:, 1].to(torch.int32)
+            probs = self.engine.tag_frames(audio, lens, window)
+            ev = self.engine.tag_events(probs, lens, threshold, off, shortest, gap, max_events)
+            bsize, m = int(probs.shape[0]), int(max_events)
+            n_tags = int(probs.shape[2])
+            # one transfer: per (clip, tag) its count, then the spans, the peaks' bits and the peak frames of its slots
+            table = torch.cat([ev["counts"].reshape(bsize, n_tags, 1), ev["spans"].reshape(bsize, n_tags, 2 * m),
+                               ev["peaks"].view(torch.int32), ev["peak_frames"]], dim=2).cpu().numpy()
+            counts = table[:, :, 0]
+            spans = table[:, :, 1:1 + 2 * m].reshape(bsize, n_tags, m, 2)
+            peaks = np.ascontiguousarray(table[:, :, 1 + 2 * m:1 + 3 * m]).view(np.float32)
+            peak_frames = table[:, :, 1 + 3 * m:]
+            events: List[List[Dict[str, Any]]] = []
+            for b in range(bsize):
+                found = []
+                for c, k in zip(*np.nonzero(spans[b, :, :, 0] >= 0)):
+                    if wanted is not None and int(c) not in wanted:
+                        continue
+                    found.append({"tag": self.audioset_idx_to_name.get(int(c), str(int(c))), "index": int(c),
+                                  "onset": int(spans[b, c, k, 0]) * alignment.FRAME_SEC, "offset": int(spans[b, c, k, 1]) * alignment.FRAME_SEC,
+                                  "peak": float(peaks[b, c, k]), "peak_time": (int(peak_frames[b, c, k]) + 0.5) * alignment.FRAME_SEC})
+                found.sort(key=lambda e: (e["onset"], e["index"]))
+                events.append(found)
+            outs = {"frame_probs": probs, "frame_lens": lens, "frame_sec": alignment.FRAME_SEC, "event_counts": ev["counts"],
+                    "events_truncated": torch.from_numpy((counts > m).any(axis=1)), "events": events}
+            clip_probs = keep.get("clip_probs")
+            if clip_probs is not None:
+                outs["tags_probs"] = clip_probs
+                outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
+            return outs
+
     def greedy_search(self, x, sr=None, x_shapes=None, preprocess: bool = True, bos_id: Optional[int] = None,
                       min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
                       forbid_rep_mode: Optional[str] = None) -> Tensor:

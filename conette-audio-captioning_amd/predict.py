@@ -4,6 +4,7 @@
     python -m conette_amd.predict --audio a.wav b.wav --task clotho --model_name DIR_OR_HUB_NAME \
         [--csv_export out.csv] [--precision certified|certified:BASE|bf16|bf16+f16dec|f16|mixed|mixed16|exact|fp32]
         [--sample N --temperature T --top_k K --top_p P --seed S [--consensus ngram|edit --consensus_order K]] [--align]
+        [--tag_timeline --tag_window SECONDS --tag_threshold P --tag_off_threshold P --tag_min_duration SECONDS --tag_max_gap SECONDS]
         [--beam_groups G --group_beam W --diversity_penalty L]
         [--prefix "a dog" --ban_words WORD ... --no_repeat_ngram N]
 
@@ -17,6 +18,7 @@ Audio files are PCM WAV (see preprocessor.load_audio).
 from __future__ import annotations
 
 import csv
+import json
 import logging
 import os.path as osp
 import sys
@@ -65,6 +67,19 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
                              "where in the clip the decoder listens while it predicts the word (CoNeTTEModel.align_captions).")
     parser.add_argument("--align_mass", type=float, default=0.5,
                         help="With --align: start .. end is the shortest window holding this share of the word's attention.")
+    parser.add_argument("--tag_timeline", action="store_true",
+                        help="Besides the caption, WHEN each AudioSet tag is heard in the file (CoNeTTEModel.tag_timeline): its events "
+                             "are printed, and exported as one JSON column 'tag_events'.")
+    parser.add_argument("--tag_window", type=float, default=None,
+                        help="With --tag_timeline: seconds of audio pooled around every 0.32 s frame (default 2.24).")
+    parser.add_argument("--tag_threshold", type=float, default=None,
+                        help="With --tag_timeline: the probability that opens an event (default 0.3).")
+    parser.add_argument("--tag_off_threshold", type=float, default=None,
+                        help="With --tag_timeline: an open event lasts while the probability stays at or above this (default: --tag_threshold).")
+    parser.add_argument("--tag_min_duration", type=float, default=None,
+                        help="With --tag_timeline: events shorter than this many seconds are dropped (default 0).")
+    parser.add_argument("--tag_max_gap", type=float, default=None,
+                        help="With --tag_timeline: events of one tag at most this many seconds apart are merged (default 0).")
     parser.add_argument("--beam_groups", type=int, default=0,
                         help="G > 0: diverse beam search in G groups (CoNeTTEModel.caption_diverse): G x --group_beam different captions "
                              "per file, one row each, group-major.")
@@ -105,6 +120,18 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
         import numpy as np
         from . import consensus
         consensus.check_arguments(np.zeros((1, args.sample, 1), dtype=np.int32), None, None, args.consensus, args.consensus_order)
+    tag_flags = ("tag_window", "tag_threshold", "tag_off_threshold", "tag_min_duration", "tag_max_gap")
+    if not args.tag_timeline and any(getattr(args, k) is not None for k in tag_flags):
+        raise ValueError("--tag_window / --tag_threshold / --tag_off_threshold / --tag_min_duration / --tag_max_gap go with --tag_timeline")
+    if args.tag_timeline:
+        if args.ensemble_models is not None:
+            raise ValueError("--tag_timeline reads one model's tag head; it does not go with --ensemble_models")
+        for k, v in zip(tag_flags, (2.24, 0.3, None, 0.0, 0.0)):
+            if getattr(args, k) is None:
+                setattr(args, k, v)
+        from . import tagging
+        tagging.check_arguments(window=tagging.window_frames(args.tag_window), on=args.tag_threshold, off=args.tag_off_threshold,
+                                min_frames=tagging.min_frames(args.tag_min_duration), max_gap=tagging.gap_frames(args.tag_max_gap))
     if args.beam_groups > 0 and args.sample > 0:
         raise ValueError("--beam_groups searches for different captions; it does not go with --sample")
     if args.beam_groups > 0 and args.align:
@@ -149,6 +176,20 @@ def format_alignment(fpaths: List[str], tasks: List[str], tokenizer, outs: dict)
     tokens, spans = outs["tokens"][:, 0].tolist(), outs["span_time"][:, 0].tolist()
     return [{"audio": osp.basename(f), "task": t, "word": tokenizer.id_to_token(tok), "start": f"{lo:.2f}", "end": f"{hi:.2f}"}
             for f, t, row, sp in zip(fpaths, tasks, tokens, spans) for tok, (lo, hi) in zip(row, sp) if tok not in special]
+
+
+def add_tag_events(model, args: Namespace, fpaths: List[str], results: List[dict]) -> None:
+    """``--tag_timeline``: every row of ``results`` gets its file's events as the JSON column "tag_events"; they are printed once per file."""
+    outs = model.tag_timeline(fpaths, window_s=args.tag_window, threshold=args.tag_threshold, off_threshold=args.tag_off_threshold,
+                              min_duration_s=args.tag_min_duration, max_gap_s=args.tag_max_gap)
+    by_file = {}
+    for f, events, cut in zip(fpaths, outs["events"], outs["events_truncated"].tolist()):
+        rows = [{"tag": e["tag"], "onset": round(e["onset"], 2), "offset": round(e["offset"], 2), "peak": round(e["peak"], 3)} for e in events]
+        by_file[osp.basename(f)] = json.dumps(rows)
+        listed = "\n".join(f" - {r['tag']} [{r['onset']:.2f}-{r['offset']:.2f}] peak {r['peak']:.2f}" for r in rows) or " - (none)"
+        pylog.info(f"File '{osp.basename(f)}' tag events{' (more than the 16 kept per tag)' if cut else ''}:\n{listed}")
+    for r in results:
+        r["tag_events"] = by_file[r["audio"]]
 
 
 def write_csv(path: str, results: List[dict]) -> None:
@@ -261,6 +302,8 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         for f, t, c in zip(fpaths, outs["tasks"], outs["cands"]):
             words = " ".join(f"{r['word']}[{r['start']}-{r['end']}]" for r in results if r["audio"] == osp.basename(f))
             pylog.info(f"File '{osp.basename(f)}' with task '{t}':\n - '{c}'\n - {words}")
+        if args.tag_timeline:
+            add_tag_events(model, args, fpaths, results)
         if args.csv_export is not None:
             write_csv(args.csv_export, results)
         return results
@@ -292,6 +335,8 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         results = format_results(fpaths, outs["tasks"], outs["cands"])
     for r in results:
         pylog.info(f"File '{r['audio']}' with task '{r['task']}':\n - '{r['candidate']}'")
+    if args.tag_timeline:
+        add_tag_events(model, args, fpaths, results)
     if args.csv_export is not None:
         write_csv(args.csv_export, results)
     return results

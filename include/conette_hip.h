@@ -460,6 +460,41 @@ int conette_consensus(const int32_t* preds, const int32_t* lens, const float* we
                       int32_t row_len, int32_t utility, int32_t max_order, int32_t eos_id, int32_t pad_id, float* expected,
                       int32_t* best, float* margin, float* pairwise, void* stream);
 
+/* Tag timeline: WHEN each AudioSet tag is heard in a clip (csrc/enc_tags.h; the CPU statement of both rules is
+ * conette_amd/tagging.py).  conette_tag_frames runs the clip head -- max over time + mean over time, LayerNorm, head_audioset,
+ * sigmoid -- over a window of frames around every frame instead of over the whole clip:
+ *   frame_embs : dev (B, t_audio, 768) fp32, conette_encode's output (0.32 s per frame)
+ *   frame_lens : dev (B) int32, the valid frames of each clip (clamped to 0 .. t_audio).  Frames at or beyond it are never read
+ *   window     : 1 .. CONETTE_TAG_MAX_WINDOW frames; frame t pools the frames max(0, t - (window - 1) / 2) ..
+ *                min(len, t + window / 2 + 1) - 1, summed in ascending order in fp32.  A window of 2 t_audio - 1 covers the clip at
+ *                every t: each row is then conette_encode's clip_probs
+ *   frame_probs: dev (B, t_audio, 527) fp32; rows t >= frame_lens[b] are exact zeros.  Every element is written
+ *   workspace  : conette_tag_frames_workspace_bytes(ctx, batch, t_audio) bytes (the head GEMM's operand rows)
+ * The head's product runs in the context's precision, like conette_encode's.  A decoder-only context has no clip head: CN_ERR_ARG.
+ * conette_tag_events turns probabilities into events per (clip, tag), with no context and no workspace, one thread per sequence:
+ *   frame_probs  : dev (B, t_audio, n_tags) fp32 -- conette_tag_frames' output or any other table; compared in fp32, NaN below all
+ *   on_threshold / off_threshold : finite, 0 < off <= on <= 1.  A run is a maximal stretch of frames t < len with p >= off that
+ *                  holds a frame with p >= on (hysteresis; off = on: plain thresholding)
+ *   max_gap      : >= 0; a run that starts at most max_gap frames after the (exclusive) end of the event before it joins that event
+ *   min_frames   : >= 0; after merging, an event shorter than this (end - start) is dropped
+ *   max_events   : 1 .. CONETTE_TAG_MAX_EVENTS slots per sequence, filled in time order
+ *   spans        : dev (B, n_tags, max_events, 2) int32 (start, end), end exclusive; unused slots (-1, -1)
+ *   peaks        : dev (B, n_tags, max_events) fp32, the largest p of the event (its bits); unused slots 0
+ *   peak_frames  : dev (B, n_tags, max_events) int32, the first frame that holds the peak; unused slots -1
+ *   counts       : dev (B, n_tags) int32, the true number of events, which may exceed max_events
+ * Every element of the four outputs is written by every call.  A failing call names the argument (CN_ERR_ARG; a short workspace:
+ * CN_ERR_WORKSPACE) and launches nothing.  Both calls are asynchronous on `stream`, allocate nothing, are capturable and
+ * bit-identical from run to run. */
+#define CONETTE_TAG_MAX_WINDOW 255
+#define CONETTE_TAG_MAX_EVENTS 64
+size_t conette_tag_frames_workspace_bytes(const conette_ctx* ctx, int32_t batch, int32_t t_audio);
+int conette_tag_frames(conette_ctx* ctx, const float* frame_embs, const int32_t* frame_lens, int32_t batch, int32_t t_audio,
+                       int32_t window, float* frame_probs /* (B, t_audio, 527) */, void* workspace, size_t workspace_bytes, void* stream);
+int conette_tag_events(const float* frame_probs, const int32_t* frame_lens, int32_t batch, int32_t t_audio, int32_t n_tags,
+                       float on_threshold, float off_threshold, int32_t min_frames, int32_t max_gap, int32_t max_events,
+                       int32_t* spans /* (B, n_tags, max_events, 2) */, float* peaks, int32_t* peak_frames /* (B, n_tags, max_events) */,
+                       int32_t* counts /* (B, n_tags) */, void* stream);
+
 /* a1: torchaudio.functional.resample (preprocessor.py:134-141), sinc_interpolation width 6,
  * rolloff 0.99.  in: dev (rows, n_in) fp32; out: dev (rows, n_out), n_out = ceil(n_in*new/orig). */
 int conette_resample(const float* in, int32_t rows, int32_t n_in, int32_t orig_sr, int32_t new_sr, float* out,
