@@ -782,7 +782,14 @@ extern "C" int conette_decode(conette_ctx* ctx, const float* frame_embs, const i
   a.margins = margins, a.ws = (char*)workspace;
   a.B = batch, a.Ta = t_audio, a.beam = beam, a.min_pred = min_pred, a.maxp = max_pred;
   hipStream_t s = (hipStream_t)stream;
-  return dec_graph_run(ctx, a, s, [&]() -> int { CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, s)); });
+  auto run = [&]() -> int { CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, s)); };
+  // the caller captures: the launches go into the caller's graph and the context's cache is left alone (no entry, no sighting
+  // counted, no replay, no event record -- a begin-capture on a capturing stream would switch the cache off for good, and a
+  // replay's event would only be captured, never recorded, for a later eviction to wait on)
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  CN_HIP(hipStreamIsCapturing(s, &cap));
+  if (cap != hipStreamCaptureStatusNone) return run();
+  return dec_graph_run(ctx, a, s, run);
 }
 
 // ---- ensemble beam search (dec_ensemble.h): M members decode one hypothesis tree in lockstep ----------------------------------
