@@ -15,6 +15,7 @@
 #include "mlp_sp.h"
 #include "down_fused.h"
 #include "dec_consensus.h"
+#include "dec_segments.h"
 
 static thread_local char g_err[512] = "";
 
@@ -795,6 +796,77 @@ extern "C" int conette_consensus(const int32_t* preds, const int32_t* lens, cons
   const int npairs = n_cands * (n_cands - 1) / 2;   // a wave per pair at a time, and at least a thread per candidate
   const int waves = std::min(CN_CS_MAX_WAVES, std::max(npairs, 1));
   hipLaunchKernelGGL(cn_consensus_kernel, dim3((unsigned)batch), dim3((unsigned)waves * 64), 0, (hipStream_t)stream, a);
+  CN_LAUNCH_CHECK();
+  return CN_OK;
+}
+
+// ---- caption timeline, the merge rule (dec_segments.h): no context; two launches
+extern "C" int conette_segments(const int32_t* preds, const int32_t* n_windows, const int32_t* win_spans, const float* lprobs,
+                                int32_t n_rec, int32_t w_max, int32_t row_len, int32_t utility, int32_t max_order, float threshold,
+                                int32_t max_run, int32_t max_segments, int32_t eos_id, int32_t pad_id, float* adjacency,
+                                int32_t* seg_windows, int32_t* seg_frames, int32_t* seg_rep, float* seg_agree, int32_t* counts,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  const char* bad = !preds ? "preds" : !n_windows ? "n_windows" : !win_spans ? "win_spans" : !lprobs ? "lprobs"
+                  : !seg_windows ? "seg_windows" : !seg_frames ? "seg_frames" : !seg_rep ? "seg_rep" : !seg_agree ? "seg_agree"
+                  : !counts ? "counts" : nullptr;
+  if (bad) {
+    cn_set_error("segments: %s is NULL", bad);
+    return CN_ERR_ARG;
+  }
+  if (n_rec < 1) {
+    cn_set_error("segments: n_rec=%d (expected at least 1)", n_rec);
+    return CN_ERR_ARG;
+  }
+  if (w_max < 1 || w_max > CONETTE_SEG_MAX_WINDOWS) {
+    cn_set_error("segments: w_max=%d unsupported (1..%d)", w_max, CONETTE_SEG_MAX_WINDOWS);
+    return CN_ERR_ARG;
+  }
+  if (row_len < 1 || row_len > CN_CS_MAX_LEN) {
+    cn_set_error("segments: row_len=%d unsupported (1..%d)", row_len, CN_CS_MAX_LEN);
+    return CN_ERR_ARG;
+  }
+  if (utility != CONETTE_UTILITY_NGRAM && utility != CONETTE_UTILITY_EDIT) {
+    cn_set_error("segments: utility=%d unknown (CONETTE_UTILITY_NGRAM, CONETTE_UTILITY_EDIT)", utility);
+    return CN_ERR_ARG;
+  }
+  if (max_order < 1 || max_order > 4) {
+    cn_set_error("segments: max_order=%d unsupported (1..4)", max_order);
+    return CN_ERR_ARG;
+  }
+  if (!(threshold > -INFINITY) || !(threshold < INFINITY)) {
+    cn_set_error("segments: threshold=%g must be finite", (double)threshold);
+    return CN_ERR_ARG;
+  }
+  if (max_run < 0) {
+    cn_set_error("segments: max_run=%d < 0 (0: no cap)", max_run);
+    return CN_ERR_ARG;
+  }
+  if (max_segments < 1 || max_segments > CONETTE_SEG_MAX_SEGMENTS) {
+    cn_set_error("segments: max_segments=%d unsupported (1..%d)", max_segments, CONETTE_SEG_MAX_SEGMENTS);
+    return CN_ERR_ARG;
+  }
+  const size_t pairs = (size_t)n_rec * (w_max - 1);
+  if (pairs > 0x7fffffffu) {
+    cn_set_error("segments: n_rec=%d x w_max=%d pairs in one call are too many (split the call)", n_rec, w_max);
+    return CN_ERR_ARG;
+  }
+  if (!adjacency && pairs > 0 && (!workspace || workspace_bytes < pairs * sizeof(float))) {
+    cn_set_error("segments: workspace %zu < %zu (without `adjacency` the pair utilities are kept there)", workspace ? workspace_bytes : (size_t)0,
+                 pairs * sizeof(float));
+    return CN_ERR_WORKSPACE;
+  }
+  CnSegArgs a;
+  a.preds = preds, a.n_windows = n_windows, a.win_spans = win_spans, a.lprobs = lprobs;
+  a.n_rec = n_rec, a.w_max = w_max, a.l = row_len, a.utility = utility, a.max_order = max_order, a.max_run = max_run;
+  a.max_segments = max_segments, a.eos_id = eos_id, a.pad_id = pad_id, a.threshold = threshold;
+  a.adj = adjacency ? adjacency : (float*)workspace;
+  a.seg_windows = seg_windows, a.seg_frames = seg_frames, a.seg_rep = seg_rep, a.seg_agree = seg_agree, a.counts = counts;
+  if (pairs > 0) {
+    hipLaunchKernelGGL(cn_seg_adjacency_kernel, dim3((unsigned)((pairs + CN_SEG_WAVES - 1) / CN_SEG_WAVES)), dim3(CN_SEG_WAVES * 64), 0,
+                       (hipStream_t)stream, a);
+    CN_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(cn_seg_runs_kernel, dim3((unsigned)((n_rec + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
   CN_LAUNCH_CHECK();
   return CN_OK;
 }

@@ -77,6 +77,80 @@ __device__ __forceinline__ uint32_t cs_count4(const int (&xa)[4], const int* y, 
   return cnt;
 }
 
+// ---- the per-wave routines of the rule, shared with the caption timeline's adjacency kernel (dec_segments.h).  `lane` is the
+// caller's lane; rows live in LDS; every routine is called by all 64 lanes of a wave.
+
+// content length of a row without given lengths: the tokens in front of the first eos_id or pad_id (the whole row if neither occurs)
+__device__ __forceinline__ int cs_content_len(const int* row, int L, int lane, int eos_id, int pad_id) {
+  const bool stop = lane < L && (row[lane] == eos_id || row[lane] == pad_id);
+  const unsigned long long m = __ballot(stop);
+  return m ? __ffsll((long long)m) - 1 : L;
+}
+
+// lane a's occurrence ranks, packed per order: how many positions b < a of the same content hold the n-gram at a
+__device__ __forceinline__ uint32_t cs_ranks(const int* row, int len, int lane) {
+  int xa[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) xa[k] = lane + k < len ? row[lane + k] : 0;
+  // (positions b < lane: the loop runs to the wave's longest need and each lane masks its own tail)
+  int yb[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) yb[k] = k < len ? row[k] : 0;
+  uint32_t rank = 0;
+  for (int b = 0; b + 1 < len; ++b) {
+    const uint32_t hit = cs_match4(xa, yb, len - b);
+    rank += b < lane ? hit : 0u;
+    yb[0] = yb[1];
+    yb[1] = yb[2];
+    yb[2] = yb[3];
+    yb[3] = b + 4 < len ? row[b + 4] : 0;
+  }
+  return rank;
+}
+
+// u(i, j) of the n-gram utility; `rank` is lane's cs_ranks of c_i
+__device__ __forceinline__ float cs_pair_ngram(const int* ci, int li, const int* cj, int lj, uint32_t rank, int lane, int max_order) {
+  int xa[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) xa[k] = lane + k < li ? ci[lane + k] : 0;
+  const uint32_t cnt = cs_count4(xa, cj, lj, lj);
+  float sum = 0.0f;
+  int counted = 0;
+  for (int n = 1; n <= max_order; ++n) {
+    const int ti = max(li - n + 1, 0), tj = max(lj - n + 1, 0);
+    const int sh = 8 * (n - 1);
+    const bool in = lane < ti && ((cnt >> sh) & 0xffu) > ((rank >> sh) & 0xffu);
+    const int m = __popcll(__ballot(in));
+    if (ti + tj > 0) {
+      sum = cs_add(sum, cs_div((float)(2 * m), (float)(ti + tj)));
+      ++counted;
+    }
+  }
+  return counted ? cs_div(sum, (float)counted) : 1.0f;
+}
+
+// u(i, j) of the edit utility.  Lane a owns DP row a + 1 (token ci[a]); on diagonal d it fills column col = d - (a + 1) when
+// 1 <= col <= lj.  `cur` is the row's newest cell (column 0 at the start: a + 1), `up` the newest cell of the row above (one diagonal
+// behind), `diag` the `up` of the diagonal before.  Row 0 is the column index itself.
+__device__ __forceinline__ float cs_pair_edit(const int* ci, int li, const int* cj, int lj, int lane) {
+  const int row = lane + 1;
+  const int x = lane < li ? ci[lane] : 0;
+  int cur = row, diag = lane;
+  for (int d = 2; d <= li + lj; ++d) {
+    const int col = d - row;
+    int up = __shfl_up(cur, 1);
+    if (lane == 0) up = col;
+    if (lane < li && col >= 1 && col <= lj) {
+      const int sub = diag + (x != cj[col - 1]);
+      cur = min(min(up, cur) + 1, sub);
+    }
+    diag = lane == 0 ? col : up;
+  }
+  const int lev = li == 0 ? lj : __shfl(cur, li - 1);
+  const int big = max(li, lj);
+  return big ? cs_sub(1.0f, cs_div((float)lev, (float)big)) : 1.0f;
+}
+
 __global__ __launch_bounds__(CN_CS_MAX_WAVES * 64) void cn_consensus_kernel(CnConsensusArgs A) {
   __shared__ int s_ids[CN_CS_MAX_CANDS * CN_CS_MAX_LEN];
   __shared__ uint32_t s_rank[CN_CS_MAX_CANDS * CN_CS_MAX_LEN];
@@ -101,9 +175,7 @@ __global__ __launch_bounds__(CN_CS_MAX_WAVES * 64) void cn_consensus_kernel(CnCo
       len = min(max(A.lens[clip * N + c], 0), L);
       if (len > 0 && row[len - 1] == A.eos_id) --len;
     } else {
-      const bool stop = lane < L && (row[lane] == A.eos_id || row[lane] == A.pad_id);
-      const unsigned long long m = __ballot(stop);
-      len = m ? __ffsll((long long)m) - 1 : L;
+      len = cs_content_len(row, L, lane, A.eos_id, A.pad_id);
     }
     if (lane == 0) s_len[c] = len;
   }
@@ -113,23 +185,7 @@ __global__ __launch_bounds__(CN_CS_MAX_WAVES * 64) void cn_consensus_kernel(CnCo
   if (A.utility == 0) {
     for (int c = wave; c < N; c += nwaves) {
       const int* row = s_ids + c * L;
-      const int len = s_len[c];
-      int xa[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) xa[k] = lane + k < len ? row[lane + k] : 0;
-      // (positions b < lane: the loop runs to the wave's longest need and each lane masks its own tail)
-      int yb[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) yb[k] = k < len ? row[k] : 0;
-      uint32_t rank = 0;
-      for (int b = 0; b + 1 < len; ++b) {
-        const uint32_t hit = cs_match4(xa, yb, len - b);
-        rank += b < lane ? hit : 0u;
-        yb[0] = yb[1];
-        yb[1] = yb[2];
-        yb[2] = yb[3];
-        yb[3] = b + 4 < len ? row[b + 4] : 0;
-      }
+      const uint32_t rank = cs_ranks(row, s_len[c], lane);
       if (lane < L) s_rank[c * L + lane] = rank;
     }
   }
@@ -149,46 +205,10 @@ __global__ __launch_bounds__(CN_CS_MAX_WAVES * 64) void cn_consensus_kernel(CnCo
     const int* cj = s_ids + j * L;
     const int li = s_len[i], lj = s_len[j];
     float u;
-    if (A.utility == 0) {
-      int xa[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) xa[k] = lane + k < li ? ci[lane + k] : 0;
-      const uint32_t cnt = cs_count4(xa, cj, lj, lj);
-      const uint32_t rank = lane < L ? s_rank[i * L + lane] : 0u;
-      float sum = 0.0f;
-      int counted = 0;
-      for (int n = 1; n <= A.max_order; ++n) {
-        const int ti = max(li - n + 1, 0), tj = max(lj - n + 1, 0);
-        const int sh = 8 * (n - 1);
-        const bool in = lane < ti && ((cnt >> sh) & 0xffu) > ((rank >> sh) & 0xffu);
-        const int m = __popcll(__ballot(in));
-        if (ti + tj > 0) {
-          sum = cs_add(sum, cs_div((float)(2 * m), (float)(ti + tj)));
-          ++counted;
-        }
-      }
-      u = counted ? cs_div(sum, (float)counted) : 1.0f;
-    } else {
-      // lane a owns DP row a + 1 (token ci[a]); on diagonal d it fills column col = d - (a + 1) when 1 <= col <= lj.  `cur` is the row's
-      // newest cell (column 0 at the start: a + 1), `up` the newest cell of the row above (one diagonal behind), `diag` the `up`
-      // of the diagonal before.  Row 0 is the column index itself.
-      const int row = lane + 1;
-      const int x = lane < li ? ci[lane] : 0;
-      int cur = row, diag = lane;
-      for (int d = 2; d <= li + lj; ++d) {
-        const int col = d - row;
-        int up = __shfl_up(cur, 1);
-        if (lane == 0) up = col;
-        if (lane < li && col >= 1 && col <= lj) {
-          const int sub = diag + (x != cj[col - 1]);
-          cur = min(min(up, cur) + 1, sub);
-        }
-        diag = lane == 0 ? col : up;
-      }
-      const int lev = li == 0 ? lj : __shfl(cur, li - 1);
-      const int big = max(li, lj);
-      u = big ? cs_sub(1.0f, cs_div((float)lev, (float)big)) : 1.0f;
-    }
+    if (A.utility == 0)
+      u = cs_pair_ngram(ci, li, cj, lj, lane < L ? s_rank[i * L + lane] : 0u, lane, A.max_order);
+    else
+      u = cs_pair_edit(ci, li, cj, lj, lane);
     if (lane == 0) {
       s_u[i * CN_CS_USTRIDE + j] = u;
       s_u[j * CN_CS_USTRIDE + i] = u;

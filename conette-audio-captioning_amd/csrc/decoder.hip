@@ -11,7 +11,7 @@
 //   * EOS floor, forbid-repeat mask, log-softmax, running sums, per-clip top-k and the
 //     finished / shrinking-k bookkeeping run in one kernel per step with no host sync.
 // This file is the host side: workspace, launch sequences, the hipGraph cache and the entry points.  The device code is in
-// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_constrain.h, dec_require.h, dec_ensemble.h, dec_block.h, dec_ffn.h, dec_score.h and dec_align.h.
+// dec_rows.h (row-wise kernels), dec_search.h (search step), dec_sample.h, dec_group.h, dec_constrain.h, dec_require.h, dec_ensemble.h, dec_block.h, dec_ffn.h, dec_score.h, dec_align.h and dec_spans.h.
 #include "ctx.h"
 #include <stdlib.h>
 
@@ -28,6 +28,7 @@
 #include "dec_require.h"
 #include "dec_align.h"
 #include "dec_ensemble.h"
+#include "dec_spans.h"
 
 #define FF2_SPLITS 8
 static int ff2_splits_default() { return 4; }  // split-K slabs of the unfused FFN2 GEMM at small R
@@ -149,6 +150,10 @@ struct DecArgs {
   // own cache: the flag of every member is part of the key, so a graph with the other sequence is never replayed
   int ens_unfused[CN_MAX_MEMBERS];
   float* ens_step_logits;  // optional
+  // conette_decode_spans (dec_spans.h): B == n_spans clips of Ta == t_span frames, gathered on the device from n_rec recordings of
+  // t_rec frames by the table `spans`; frame_lens is null (the gather writes the lengths).  All zero on every other path.
+  const int32_t* spans;
+  int n_rec, t_rec, n_spans;
   bool operator==(const DecArgs& o) const { return memcmp(this, &o, sizeof(DecArgs)) == 0; }
 };
 
@@ -167,6 +172,43 @@ static int dec_prepare(conette_ctx* ctx, const float* frame_embs, int B, int Ta,
   CN_TRY(cn_mm(fe_t, CN_FEAT, (const T*)ctx->proj_w, CN_FEAT, B * Ta, d, CN_FEAT, ep, s));
   EpiBiasAct<T, ACT_NONE> ekv{ctx->kv_b, (T*)w.kvc, kv_ld, ACT_NONE};
   CN_TRY(cn_mm(mem, d, (const T*)ctx->kv_w, d, B * Ta, kv_ld, d, ekv, s));
+  return CN_OK;
+}
+
+// ---- conette_decode_spans: dec_prepare once over the recordings, then the spans' K/V rows gathered into w.kvc ----------------
+// Behind the search's workspace (w.total): the recordings' converted frames, projected memory and cross K/V, and the spans' lengths.
+struct SpanWs {
+  void *fe_t, *mem, *kvc;
+  int32_t* lens;
+  size_t total;
+};
+static SpanWs span_ws(const conette_ctx* ctx, int n_rec, int t_rec, int n_spans, char* base) {
+  const size_t es = ctx->esize, rows = (size_t)n_rec * t_rec;
+  const int d = ctx->cfg.d_model;
+  SpanWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += cn_align(bytes);
+    return p;
+  };
+  w.fe_t = take(rows * CN_FEAT * es);
+  w.mem = take(rows * d * es);
+  w.kvc = take(rows * ctx->cfg.n_layers * 2 * d * es);
+  w.lens = (int32_t*)take((size_t)n_spans * 4);
+  w.total = off;
+  return w;
+}
+template <typename T>
+static int dec_prepare_spans(conette_ctx* ctx, const DecArgs& a, const DecWs& w, const SpanWs& sw, hipStream_t s) {
+  DecWs rec = w;  // (dec_prepare reads these three members only)
+  rec.fe_t = sw.fe_t, rec.mem = sw.mem, rec.kvc = sw.kvc;
+  CN_TRY(dec_prepare<T>(ctx, a.frame_embs, a.n_rec, a.t_rec, rec, s));
+  CnProfScope ps(ctx, CONETTE_PROF_DEC_PREPARE, s);
+  const int row_vecs = (int)((size_t)ctx->cfg.n_layers * 2 * ctx->cfg.d_model * ctx->esize / 16);
+  hipLaunchKernelGGL(cn_span_gather_kernel, dim3((unsigned)a.Ta, (unsigned)a.n_spans), dim3(256), 0, s, (const uint4*)sw.kvc, a.spans,
+                     a.n_rec, a.t_rec, a.Ta, row_vecs, (uint4*)w.kvc, sw.lens);
+  CN_LAUNCH_CHECK();
   return CN_OK;
 }
 
@@ -400,7 +442,14 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
   const bool sampling = a.uniforms != nullptr;
   const unsigned long long* kvalid = forcing ? w.kvalid : nullptr;
 
-  CN_TRY(dec_prepare<T>(ctx, a.frame_embs, B, Ta, w, s));
+  const int32_t* frame_lens = a.frame_lens;
+  if (a.spans) {  // conette_decode_spans: the clips are spans of recordings; their lengths come from the gather
+    const SpanWs sw = span_ws(ctx, a.n_rec, a.t_rec, a.n_spans, a.ws + w.total);
+    CN_TRY(dec_prepare_spans<T>(ctx, a, w, sw, s));
+    frame_lens = sw.lens;
+  } else {
+    CN_TRY(dec_prepare<T>(ctx, a.frame_embs, B, Ta, w, s));
+  }
   hipLaunchKernelGGL(cn_init_state_kernel, dim3(64), dim3(256), 0, s, B, beam, maxp, a.bos_ids, w.n_active, w.slot,
                      w.sum_lp, w.prefix, w.anc, w.cur_tok, a.mult_preds, a.mult_lprobs, w.out_len, a.out_sizes, cfg.pad_id,
                      a.trace_sel, a.trace_val, w.live, a.margins);
@@ -449,7 +498,7 @@ static int decode_impl(conette_ctx* ctx, const DecArgs& a, hipStream_t s) {
     // (beam.py:192-194); the launch sequence is static (hipGraph), so the heavy kernels of the remaining steps read the
     // number of rows still searching and return at once
     const int* gate = (!forcing && step > 0) ? w.live + step : nullptr;
-    CN_TRY(dec_step_forward<T>(ctx, w, w.cur_tok, w.anc, gate, kvalid, a.frame_lens, B, Ta, beam, maxp, step, db_debug, s));
+    CN_TRY(dec_step_forward<T>(ctx, w, w.cur_tok, w.anc, gate, kvalid, frame_lens, B, Ta, beam, maxp, step, db_debug, s));
     if (step == 0 && a.step0_logits)
       CN_HIP(hipMemcpyAsync(a.step0_logits, w.logits, (size_t)R * w.ldv * 4, hipMemcpyDeviceToDevice, s));
     if (forcing) {
@@ -943,6 +992,73 @@ extern "C" int32_t conette_decode_graph_nodes(const conette_ctx* ctx) {
   if (!c) return 0;
   std::lock_guard<std::mutex> lock(c->mu);
   return c->last_nodes;
+}
+
+// ---- beam search over spans of recordings encoded once (dec_spans.h) ----
+// The limits of one call: the GEMM epilogues and the attention kernels index rows * kv_ld elements in 32 bits, and the gather's grid
+// has one y-block per span.
+static bool spans_shape_ok(const conette_ctx* ctx, long n_rec, long t_rec, long n_spans, long t_span) {
+  const long kv_ld = (long)ctx->cfg.n_layers * 2 * ctx->cfg.d_model;
+  const long wide = kv_ld > CN_FEAT ? kv_ld : CN_FEAT;
+  return n_rec * t_rec <= 0x7fffffffL / wide && n_spans * t_span <= 0x7fffffffL / wide && n_spans <= 65535;
+}
+extern "C" size_t conette_decode_spans_workspace_bytes(const conette_ctx* ctx, int32_t n_rec, int32_t t_rec, int32_t n_spans,
+                                                       int32_t t_span, int32_t beam, int32_t max_pred) {
+  if (!ctx || n_rec <= 0 || t_rec <= 0 || n_spans <= 0 || t_span <= 0 || max_pred <= 0 || beam < 1 || beam > CN_MAX_BEAM) return 0;
+  if (!spans_shape_ok(ctx, n_rec, t_rec, n_spans, t_span)) return 0;
+  return dec_ws(ctx, n_spans, t_span, beam, max_pred, nullptr).total + span_ws(ctx, n_rec, t_rec, n_spans, nullptr).total;
+}
+
+extern "C" int conette_decode_spans(conette_ctx* ctx, const float* frame_embs, const int32_t* spans, const int32_t* bos_ids,
+                                    const uint8_t* forbid_mask, int32_t n_rec, int32_t t_rec, int32_t n_spans, int32_t t_span,
+                                    int32_t beam, int32_t min_pred, int32_t max_pred, int32_t* best_preds, float* best_lprobs,
+                                    int32_t* mult_preds, float* mult_lprobs, int32_t* out_sizes, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  const char* who = "decode_spans";
+  const char* missing = !ctx ? "ctx" : !frame_embs ? "frame_embs" : !spans ? "spans" : !bos_ids ? "bos_ids" : !best_preds ? "best_preds"
+                      : !best_lprobs ? "best_lprobs" : !mult_preds ? "mult_preds" : !mult_lprobs ? "mult_lprobs"
+                      : !out_sizes ? "out_sizes" : !workspace ? "workspace" : nullptr;
+  if (missing) {
+    cn_set_error("%s: %s is NULL", who, missing);
+    return CN_ERR_ARG;
+  }
+  if (n_rec < 1 || t_rec < 1) {
+    cn_set_error("%s: n_rec=%d t_rec=%d (both at least 1)", who, n_rec, t_rec);
+    return CN_ERR_ARG;
+  }
+  if (n_spans < 1) {
+    cn_set_error("%s: n_spans=%d (expected at least 1)", who, n_spans);
+    return CN_ERR_ARG;
+  }
+  if (t_span < 1) {
+    cn_set_error("%s: t_span=%d (expected at least 1)", who, t_span);
+    return CN_ERR_ARG;
+  }
+  if (beam < 1 || beam > CN_MAX_BEAM) {
+    cn_set_error("%s: beam=%d unsupported (1..%d)", who, beam, CN_MAX_BEAM);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_model(ctx, who, max_pred, min_pred, "%s: max_pred=%d (1..%d) min_pred=%d unsupported", who, max_pred, CN_MAX_PRED,
+                         min_pred));
+  if (!spans_shape_ok(ctx, n_rec, t_rec, n_spans, t_span)) {
+    cn_set_error("%s: n_rec=%d x t_rec=%d frames or n_spans=%d x t_span=%d frames in one call are too many (split the call)", who, n_rec,
+                 t_rec, n_spans, t_span);
+    return CN_ERR_ARG;
+  }
+  CN_TRY(dec_check_workspace(who, workspace_bytes, conette_decode_spans_workspace_bytes(ctx, n_rec, t_rec, n_spans, t_span, beam, max_pred)));
+  DecArgs a;
+  memset(&a, 0, sizeof(a));  // (padding included: the record is the graph key)
+  a.frame_embs = frame_embs, a.bos_ids = bos_ids, a.forbid = forbid_mask;
+  a.best_preds = best_preds, a.best_lprobs = best_lprobs, a.mult_preds = mult_preds, a.mult_lprobs = mult_lprobs;
+  a.out_sizes = out_sizes, a.ws = (char*)workspace;
+  a.B = n_spans, a.Ta = t_span, a.beam = beam, a.min_pred = min_pred, a.maxp = max_pred;
+  a.spans = spans, a.n_rec = n_rec, a.t_rec = t_rec, a.n_spans = n_spans;
+  hipStream_t s = (hipStream_t)stream;
+  auto run = [&]() -> int { CN_BY_PRECISION(ctx, decode_impl<OT>(ctx, a, s)); };
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;  // (the caller captures: as conette_decode)
+  CN_HIP(hipStreamIsCapturing(s, &cap));
+  if (cap != hipStreamCaptureStatusNone) return run();
+  return dec_graph_run(ctx, a, s, run);
 }
 
 // ---- teacher forcing as ONE causal pass (nn/decoding/forcing.py:12-71 is a single decoder forward over the caption) ----

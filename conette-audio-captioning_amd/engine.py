@@ -38,6 +38,7 @@ EXPORTS = (
     "conette_decode_required_workspace_bytes", "conette_decode_required",
     "conette_decode_ensemble_workspace_bytes", "conette_decode_ensemble", "conette_consensus",
     "conette_tag_frames_workspace_bytes", "conette_tag_frames", "conette_tag_events",
+    "conette_decode_spans_workspace_bytes", "conette_decode_spans", "conette_segments",
 )
 # ---- precision "certified": when is a 16-bit search's decision as good as an exact one's? ------------------------------------
 # Per base precision and kind of search, (a, b, c): the top-k call of step i is certified when its margin is at least
@@ -223,6 +224,16 @@ def load_library() -> C.CDLL:
     lib.conette_tag_events.restype = C.c_int
     lib.conette_tag_events.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.conette_decode_spans_workspace_bytes.restype = C.c_size_t
+    lib.conette_decode_spans_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.conette_decode_spans.restype = C.c_int
+    lib.conette_decode_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.conette_segments.restype = C.c_int
+    lib.conette_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     if lib.conette_abi_version() != 3:
         raise RuntimeError("libconette_hip.so ABI version mismatch")
     _lib = lib
@@ -490,10 +501,12 @@ class Engine:
 
     # ---- a9-a14 ----------------------------------------------------------------------------
     def _decode_buffers(self, b: int, t: int, beam: int, max_pred: int, s0: bool, trace: bool,
-                        slot: int = 0, margins: bool = False, exact: bool = False) -> Dict[str, Any]:
+                        slot: int = 0, margins: bool = False, exact: bool = False,
+                        spans: Optional[Tuple[int, int]] = None) -> Dict[str, Any]:
         """Persistent I/O buffers per shape (and pipeline slot): identical pointers let the library
-        replay its hipGraph."""
-        key = (b, t, beam, max_pred, s0, trace, slot, margins, exact)
+        replay its hipGraph.  ``spans`` = (n_rec, t_rec): the buffers of decode_spans -- b spans of t frames, "fe" holds the
+        recordings and "spans" the table."""
+        key = (b, t, beam, max_pred, s0, trace, slot, margins, exact) + (() if spans is None else ("spans",) + tuple(spans))
         buf = self._dec_bufs.pop(key, None)
         if buf is not None:
             self._dec_bufs[key] = buf           # least recently used first: a hit moves to the back
@@ -502,7 +515,8 @@ class Engine:
             ldv = (self.vocab_size + 7) // 8 * 8
             e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
             buf = {
-                "fe": e((b, t, FEAT), torch.float32), "lens": e((b,), torch.int32), "bos": e((b,), torch.int32),
+                "fe": e((b, t, FEAT) if spans is None else (spans[0], spans[1], FEAT), torch.float32),
+                "lens": e((b,), torch.int32), "spans": None if spans is None else e((b, 3), torch.int32), "bos": e((b,), torch.int32),
                 "forbid": e((self.vocab_size,), torch.uint8),
                 "best_preds": e((b, max_pred), torch.int32), "best_lprobs": e((b,), torch.float32),
                 "mult_preds": e((b, beam, max_pred), torch.int32), "mult_lprobs": e((b, beam), torch.float32),
@@ -1182,6 +1196,94 @@ class Engine:
         st = self.lib.conette_tag_events(_ptr(p), _ptr(lens), b, t, c, float(on), float(off), int(min_frames), int(max_gap), m,
                                          _ptr(out["spans"]), _ptr(out["peaks"]), _ptr(out["peak_frames"]), _ptr(out["counts"]), _stream())
         _check(st, "conette_tag_events")
+        return out
+
+    # ---- caption timeline: conette_decode_spans / conette_segments; the grid and the rule: segments.py --------------------------------
+    def decode_spans(self, frame_embs: torch.Tensor, frame_lens: torch.Tensor, spans, bos_ids: torch.Tensor,
+                     forbid_mask: Optional[torch.Tensor], beam: int, min_pred: int, max_pred: int, t_span: Optional[int] = None,
+                     clone: bool = True) -> Dict[str, torch.Tensor]:
+        """Beam search over spans of recordings that were encoded once (conette_decode_spans, include/conette_hip.h).
+        frame_embs (N, t_rec, 768), frame_lens (N,) valid frames, ``spans`` (S, 3) rows of (recording, start, len) in frames -- held
+        to ``segments.check_spans`` here, on the host, so ``frame_lens`` and ``spans`` are read back if they live on the device --,
+        bos_ids (S,).  ``t_span`` (default: the longest len) is the width of the span axis.  Returns ``decode``'s dict over the S
+        spans plus "spans", the table as the device read it.  The I/O buffers are persistent per shape, so that the library replays
+        its hipGraph: a later call with another table of the same shape only rewrites the table's contents.  A certified engine
+        searches on its 16-bit base context."""
+        import numpy as np
+        from . import segments as rule
+        if frame_embs.ndim != 3 or frame_embs.shape[2] != FEAT:
+            raise ValueError(f"decode_spans: frame_embs of shape {tuple(frame_embs.shape)} (expected (n_rec, t_rec, {FEAT}))")
+        n, t_rec = int(frame_embs.shape[0]), int(frame_embs.shape[1])
+        lens_h = torch.as_tensor(frame_lens).detach().cpu().reshape(-1).numpy()
+        if lens_h.shape[0] != n:
+            raise ValueError(f"decode_spans: frame_lens of {lens_h.shape[0]} entries for {n} recordings")
+        if lens_h.size and (lens_h.min() < 0 or lens_h.max() > t_rec):
+            raise ValueError(f"decode_spans: frame_lens must lie in 0..t_rec={t_rec}")
+        table_h = spans.detach().cpu().numpy() if isinstance(spans, torch.Tensor) else np.asarray(spans)
+        if t_span is None:
+            t_span = int(table_h[:, 2].max()) if table_h.ndim == 2 and table_h.shape[0] > 0 and table_h.shape[1] == 3 else 0
+        table_h = rule.check_spans(table_h, n, lens_h, int(t_span))
+        s_n, t_span = int(table_h.shape[0]), int(t_span)
+        if tuple(bos_ids.shape) != (s_n,):
+            raise ValueError(f"decode_spans: bos_ids of shape {tuple(bos_ids.shape)} for {s_n} spans")
+        ctx = self._ctx_dec
+        beam, max_pred = int(beam), int(max_pred)
+        buf = self._decode_buffers(s_n, t_span, beam, max_pred, False, False, spans=(n, t_rec))
+        if frame_embs.data_ptr() != buf["fe"].data_ptr():
+            buf["fe"].copy_(frame_embs, non_blocking=True)
+        buf["spans"].copy_(torch.from_numpy(table_h), non_blocking=False)
+        buf["bos"].copy_(bos_ids.to(torch.int32), non_blocking=True)
+        forbid_ptr = None
+        if forbid_mask is not None:
+            if forbid_mask.numel() != self.vocab_size:
+                raise ValueError("forbid_mask must have vocab_size entries")
+            buf["forbid"].copy_(forbid_mask.to(torch.uint8), non_blocking=True)
+            forbid_ptr = buf["forbid"]
+        need = int(self.lib.conette_decode_spans_workspace_bytes(ctx, n, t_rec, s_n, t_span, beam, max_pred))
+        wsb = self._workspace("dec_spans", max(need, 1))
+        st = self.lib.conette_decode_spans(ctx, _ptr(buf["fe"]), _ptr(buf["spans"]), _ptr(buf["bos"]), _ptr(forbid_ptr), n, t_rec, s_n,
+                                           t_span, beam, int(min_pred), max_pred, _ptr(buf["best_preds"]), _ptr(buf["best_lprobs"]),
+                                           _ptr(buf["mult_preds"]), _ptr(buf["mult_lprobs"]), _ptr(buf["sizes"]), _ptr(wsb),
+                                           wsb.numel() if need else 0, _stream())
+        _check(st, "conette_decode_spans")
+        cp = (lambda x: x.clone()) if clone else (lambda x: x)
+        return {k: cp(buf[k]) for k in ("best_preds", "best_lprobs", "mult_preds", "mult_lprobs", "sizes", "spans")}
+
+    def segments(self, preds: torch.Tensor, n_windows: torch.Tensor, lprobs: torch.Tensor, win_spans: torch.Tensor,
+                 utility: str = "ngram", max_order: int = 4, threshold: float = 0.5, max_run: int = 0, max_segments: int = 64,
+                 adjacency: bool = True) -> Dict[str, torch.Tensor]:
+        """The merge rule over recordings (conette_segments; the rule: segments.merge_batch): ``preds`` (N, Wmax, L) the windows'
+        best captions, ``n_windows`` (N,), ``lprobs`` (N, Wmax), ``win_spans`` (N, Wmax, 2) (start, len) in frames ->
+        {"seg_windows", "seg_frames": (N, max_segments, 2) int32, "seg_rep": (N, max_segments) int32, "seg_agree":
+        (N, max_segments) fp32, "counts": (N,) int32 [, "adjacency": (N, Wmax - 1) fp32]} on the device; no host sync."""
+        from . import segments as rule
+        if preds.ndim != 3:
+            raise ValueError(f"segments: preds of shape {tuple(preds.shape)} (expected (n_rec, w_max, row_len))")
+        n, wmax, l = (int(v) for v in preds.shape)
+        if n < 1:
+            raise ValueError("segments: no recording")
+        code = rule.check_arguments(l, wmax, utility, max_order, threshold, max_run, max_segments)
+        for name, t, shape in (("n_windows", n_windows, (n,)), ("lprobs", lprobs, (n, wmax)), ("win_spans", win_spans, (n, wmax, 2))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"segments: {name} of shape {tuple(t.shape)} for preds of shape {(n, wmax, l)} (expected {shape})")
+        ids = preds.to(self.device, torch.int32).contiguous()
+        nw = n_windows.to(self.device, torch.int32).contiguous()
+        lp = lprobs.to(self.device, torch.float32).contiguous()
+        sp = win_spans.to(self.device, torch.int32).contiguous()
+        m = int(max_segments)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        out = {"seg_windows": e((n, m, 2), torch.int32), "seg_frames": e((n, m, 2), torch.int32), "seg_rep": e((n, m), torch.int32),
+               "seg_agree": e((n, m), torch.float32), "counts": e((n,), torch.int32)}
+        wsb = None
+        if adjacency:
+            out["adjacency"] = e((n, wmax - 1), torch.float32)
+        elif wmax > 1:
+            wsb = self._workspace("segments", n * (wmax - 1) * 4)
+        st = self.lib.conette_segments(_ptr(ids), _ptr(nw), _ptr(sp), _ptr(lp), n, wmax, l, code, int(max_order), float(threshold),
+                                       int(max_run), m, self.eos_id, self.pad_id, _ptr(out.get("adjacency")), _ptr(out["seg_windows"]),
+                                       _ptr(out["seg_frames"]), _ptr(out["seg_rep"]), _ptr(out["seg_agree"]), _ptr(out["counts"]),
+                                       _ptr(wsb), 0 if wsb is None else wsb.numel(), _stream())
+        _check(st, "conette_segments")
         return out
 
     # ---- a1 --------------------------------------------------------------------------------

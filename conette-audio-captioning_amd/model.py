@@ -990,6 +990,188 @@ class CoNeTTEModel:
                 outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
             return outs
 
+    # ---- caption timeline: captions of spans of recordings encoded once (conette_decode_spans) and their merge into segments
+    # (conette_segments); the grid and the rule: segments.py
+    def _span_search(self, audio, lens_h, table, tasks, dataset_lst, source_lst, beam_size, min_pred_size, max_pred_size, forbid_rep_mode):
+        """One decode_spans over ``table`` (S, 3); (device outputs, pred_size, best_maxlen)"""
+        cfg = self.config
+        beam = cfg.beam_size if beam_size is None else int(beam_size)
+        min_pred = cfg.min_pred_size if min_pred_size is None else int(min_pred_size)
+        max_pred = cfg.max_pred_size if max_pred_size is None else int(max_pred_size)
+        bos = self.batch_to_task_token_ids(dataset_lst, source_lst)[torch.from_numpy(table[:, 0].astype("int64"))]
+        res = self.engine.decode_spans(audio, torch.from_numpy(lens_h), table, bos, self.get_forbid_rep_mask(forbid_rep_mode), beam,
+                                       min_pred, max_pred)
+        pred_size, best_maxlen = (int(v) for v in res["sizes"].tolist())
+        return res, pred_size, best_maxlen
+
+    @staticmethod
+    def _span_list(spans) -> List[List[tuple]]:
+        """``caption_spans``' argument as frames: per recording a list of (start, len); ValueError for what no recording can hold"""
+        from . import segments
+        if spans is None or isinstance(spans, (str, bytes)) or len(spans) == 0:
+            raise ValueError("Invalid argument spans: expected, per recording, a list of (onset_s, offset_s) in seconds.")
+        out = []
+        for r, rows in enumerate(spans):
+            rows = list(rows)
+            if not rows:
+                raise ValueError(f"Invalid argument spans: recording {r} has no span.")
+            conv = []
+            for k, row in enumerate(rows):
+                if len(row) != 2:
+                    raise ValueError(f"Invalid argument spans: spans[{r}][{k}]={row!r} is not an (onset_s, offset_s) pair.")
+                try:
+                    conv.append(segments.seconds_to_span(row[0], row[1]))
+                except ValueError as e:
+                    raise ValueError(f"Invalid argument spans: spans[{r}][{k}]: {e}") from None
+            out.append(conv)
+        return out
+
+    @torch.no_grad()
+    def caption_spans(self, x, spans, task: Union[str, List[str], None] = None, beam_size: Optional[int] = None,
+                      min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None, forbid_rep_mode: Optional[str] = None,
+                      sr=None, x_shapes=None, preprocess: bool = True) -> Dict[str, Any]:
+        """Captions of given spans of (long) recordings: one encode, then ONE beam search whose clips are the spans
+        (conette_decode_spans): the projection and the cross-attention keys / values run once per recording frame, however many
+        spans hold it.  ``x`` as in ``score_captions``; ``spans`` holds, per recording, a list of (onset_s, offset_s) in seconds
+        from the recording's start -- for instance the events of ``tag_timeline`` -- rounded half up to 0.32 s frames, at least one
+        frame each; an offset beyond the recording's end is cut there, an onset at or beyond it raises.  ``task`` (one per
+        recording) and the search arguments as in ``forward``.  Returns ``forward``'s keys per recording as lists over its spans --
+        "cands", "mult_cands": lists of strings; "preds" (n_r, best_maxlen), "lprobs" (n_r,), "mult_preds" (n_r, beam, pred_size),
+        "mult_lprobs" (n_r, beam): tensors per recording --, "tasks", and "span_frames": per recording an (n_r, 2) tensor of
+        (start, len) in frames.  A span's caption sees the encoder's context beyond the span (its receptive field covers several
+        seconds): it is not the caption of the cut waveform.  Precision "certified" runs on its 16-bit base context, with no exact
+        re-run, like ``score_captions``; an overflow of the 16-bit encoders raises as in ``tag_timeline``."""
+        import numpy as np
+        frames = CoNeTTEModel._span_list(spans)
+        with torch.cuda.device(self.device):
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess)
+            self._refuse_encoder_overflow(preprocess)
+            bsize = int(audio.shape[0])
+            if len(frames) != bsize:
+                raise ValueError(f"Invalid argument spans: {len(frames)} lists of spans for {bsize} recordings.")
+            tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
+            lens_h = torch.as_tensor(audio_shape)[:, 1].to(torch.int32).cpu().numpy()
+            rows = []
+            for r, conv in enumerate(frames):
+                for k, (start, ln) in enumerate(conv):
+                    if start >= int(lens_h[r]):
+                        raise ValueError(f"Invalid argument spans: spans[{r}][{k}] starts at frame {start}, at or beyond the "
+                                         f"{int(lens_h[r])} frames of recording {r}.")
+                    rows.append((r, start, min(ln, int(lens_h[r]) - start)))
+            table = np.asarray(rows, dtype=np.int32)
+            res, pred_size, best_maxlen = self._span_search(audio, lens_h, table, tasks, dataset_lst, source_lst, beam_size,
+                                                            min_pred_size, max_pred_size, forbid_rep_mode)
+            preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()
+            mult_preds = res["mult_preds"][:, :, :pred_size].to(torch.long).contiguous()
+            cands, mult_cands = self.tokenizer.decode_rec(preds), self.tokenizer.decode_rec(mult_preds)
+            bounds = np.concatenate([[0], np.cumsum([len(c) for c in frames])]).tolist()
+            cut = lambda v: [v[bounds[r]:bounds[r + 1]] for r in range(bsize)]
+            return {"cands": cut(cands), "preds": cut(preds), "lprobs": cut(res["best_lprobs"]), "mult_cands": cut(mult_cands),
+                    "mult_preds": cut(mult_preds), "mult_lprobs": cut(res["mult_lprobs"]), "tasks": tasks,
+                    "span_frames": cut(torch.from_numpy(table[:, 1:].copy()))}
+
+    @torch.no_grad()
+    def caption_segments(self, x, window_s: float = 10.0, hop_s: float = 5.0, merge_threshold: Optional[float] = 0.5,
+                         utility: str = "ngram", max_order: int = 4, max_run_s: float = 0.0, max_segments: int = 64,
+                         task: Union[str, List[str], None] = None, beam_size: Optional[int] = None,
+                         min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
+                         forbid_rep_mode: Optional[str] = None, threshold: Union[float, Tensor] = 0.3, sr=None, x_shapes=None,
+                         preprocess: bool = True) -> Dict[str, Any]:
+        """Captions over time -- WHAT is heard WHEN in a long recording, the caption-side counterpart of ``tag_timeline``.  The
+        recording is encoded once; windows of ``window_s`` seconds every ``hop_s`` seconds over each recording's own frames (the
+        last window aligned to its end; the grid: segments.py) are captioned by one beam search over all recordings' windows
+        (conette_decode_spans), and neighbouring windows whose captions agree are merged into segments on the device
+        (conette_segments): window k + 1 joins the run of window k iff the ``utility`` ("ngram" with ``max_order`` 1 .. 4, or "edit":
+        ``select_consensus``'s pair utilities) of their two captions is at least ``merge_threshold``; a run never grows beyond
+        ``max_run_s`` seconds (0: no cap).  ``merge_threshold=None``: one segment per window.  A segment carries the caption of its
+        most likely window; two neighbouring segments meet in the middle of the overlap of the windows on either side.
+
+        ``x`` as in ``score_captions``; ``task`` and the search arguments as in ``forward``.  Returns {"segments": per recording a
+        list, in time order, of {"onset", "offset" (seconds from the recording's start), "caption", "pred" (ids), "lprob",
+        "agreement" (the smallest utility between neighbouring windows of the segment, 1 for a single window), "windows":
+        (first, end)}; "window_cands", "window_preds", "window_lprobs", "window_times": per recording the windows' captions, ids
+        (n_r, best_maxlen), scores (n_r,) and (onset, offset) seconds; "adjacency": (N, Wmax - 1) the utilities of neighbouring
+        windows (zeros beyond a recording's windows); "segment_counts": (N,) the true numbers; "segments_truncated": (N,) bool, true
+        where a recording has more than the ``max_segments`` (1 .. 256) segments kept; "frame_sec" [, "tags_probs", "tags":
+        ``forward``'s, with ``threshold``, when the call ran the preprocessor]}.  The tables come to the host in one transfer.
+
+        The defaults -- 10 s windows, 5 s hop, threshold 0.5 -- are UNTUNED: no trained checkpoint was available to choose them on.
+        A window's caption sees the encoder's context beyond the window (its receptive field covers several seconds), so it is not
+        the caption of the cut waveform.  A recording the encoder refuses raises the library's error: nothing is chunked silently.
+        Precision "certified" runs on its 16-bit base context, with no exact re-run, like ``score_captions``; an overflow of the
+        16-bit encoders raises as in ``tag_timeline``."""
+        import numpy as np
+        from . import alignment, segments
+        window, hop = segments.window_frames(window_s), segments.hop_frames(hop_s)
+        max_run = 1 if merge_threshold is None else segments.run_windows(max_run_s, window, hop)
+        thr = 0.0 if merge_threshold is None else float(merge_threshold)
+        segments.check_arguments(1, 1, utility, max_order, thr, max_run, max_segments)
+        sec = alignment.FRAME_SEC
+        with torch.cuda.device(self.device):
+            keep: Dict[str, Any] = {}
+            audio, audio_shape = self._frame_embeddings(x, sr, x_shapes, preprocess, keep)
+            self._refuse_encoder_overflow(preprocess)
+            bsize = int(audio.shape[0])
+            tasks, dataset_lst, source_lst = self._split_tasks(task, bsize)
+            lens_h = torch.as_tensor(audio_shape)[:, 1].to(torch.int32).cpu().numpy()
+            if lens_h.min() < 1:
+                raise ValueError("caption_segments: a recording without a frame")
+            table, n_win = segments.span_table(lens_h, window, hop)
+            wmax = int(n_win.max())
+            segments.check_arguments(1, wmax, utility, max_order, thr, max_run, max_segments)   # (the window count)
+            res, pred_size, best_maxlen = self._span_search(audio, lens_h, table, tasks, dataset_lst, source_lst, beam_size,
+                                                            min_pred_size, max_pred_size, forbid_rep_mode)
+            # the windows as (N, Wmax) tables: window k of recording r is row bounds[r] + k of the search
+            bounds = np.concatenate([[0], np.cumsum(n_win)]).astype(np.int64)
+            slot = np.concatenate([np.arange(w, dtype=np.int64) + r * wmax for r, w in enumerate(n_win.tolist())])
+            slot_d = torch.from_numpy(slot).to(self.device)
+            max_pred = int(res["best_preds"].shape[1])
+            ids = torch.full((bsize * wmax, max_pred), self.tokenizer.pad_token_id, dtype=torch.int32, device=self.device)
+            ids.index_copy_(0, slot_d, res["best_preds"])
+            lp = torch.zeros((bsize * wmax,), dtype=torch.float32, device=self.device)
+            lp.index_copy_(0, slot_d, res["best_lprobs"])
+            sp = torch.zeros((bsize * wmax, 2), dtype=torch.int32)
+            sp[torch.from_numpy(slot)] = torch.from_numpy(table[:, 1:].copy())
+            m = int(max_segments)
+            seg = self.engine.segments(ids.view(bsize, wmax, max_pred), torch.from_numpy(n_win), lp.view(bsize, wmax),
+                                       sp.view(bsize, wmax, 2), utility=utility, max_order=max_order, threshold=thr, max_run=max_run,
+                                       max_segments=m)
+            # one transfer: per recording its count, the segments' windows, frames, representatives and agreement bits, the adjacency bits
+            # and the windows' score bits
+            tab = torch.cat([seg["counts"].reshape(bsize, 1), seg["seg_windows"].reshape(bsize, 2 * m), seg["seg_frames"].reshape(bsize, 2 * m),
+                             seg["seg_rep"], seg["seg_agree"].view(torch.int32), seg["adjacency"].view(torch.int32),
+                             lp.view(bsize, wmax).view(torch.int32)], dim=1).cpu().numpy()
+            counts = tab[:, 0]
+            seg_w = tab[:, 1:1 + 2 * m].reshape(bsize, m, 2)
+            seg_f = tab[:, 1 + 2 * m:1 + 4 * m].reshape(bsize, m, 2)
+            seg_rep = tab[:, 1 + 4 * m:1 + 5 * m]
+            seg_agree = np.ascontiguousarray(tab[:, 1 + 5 * m:1 + 6 * m]).view(np.float32)
+            adjacency = np.ascontiguousarray(tab[:, 1 + 6 * m:wmax + 6 * m]).view(np.float32)
+            lprobs_h = torch.from_numpy(np.ascontiguousarray(tab[:, wmax + 6 * m:]).view(np.float32).reshape(-1)[slot].copy())
+            preds = res["best_preds"][:, :best_maxlen].to(torch.long).contiguous()
+            cands = self.tokenizer.decode_rec(preds)
+            cut = lambda v: [v[int(bounds[r]):int(bounds[r + 1])] for r in range(bsize)]
+            w_cands, w_preds, w_lprobs = cut(cands), cut(preds), cut(lprobs_h)
+            found: List[List[Dict[str, Any]]] = []
+            for r in range(bsize):
+                rows = []
+                for k in range(min(int(counts[r]), m)):
+                    rep = int(seg_rep[r, k])
+                    rows.append({"onset": int(seg_f[r, k, 0]) * sec, "offset": int(seg_f[r, k, 1]) * sec, "caption": w_cands[r][rep],
+                                 "pred": w_preds[r][rep], "lprob": float(w_lprobs[r][rep]), "agreement": float(seg_agree[r, k]),
+                                 "windows": (int(seg_w[r, k, 0]), int(seg_w[r, k, 1]))})
+                found.append(rows)
+            times = [[(int(a) * sec, (int(a) + int(b)) * sec) for a, b in table[int(bounds[r]):int(bounds[r + 1]), 1:]] for r in range(bsize)]
+            outs = {"segments": found, "window_cands": w_cands, "window_preds": w_preds, "window_lprobs": w_lprobs, "window_times": times,
+                    "window_frames": cut(torch.from_numpy(table[:, 1:].copy())), "adjacency": torch.from_numpy(adjacency.copy()),
+                    "segment_counts": torch.from_numpy(counts.copy()), "segments_truncated": torch.from_numpy(counts > m),
+                    "frame_sec": sec, "tasks": tasks}
+            clip_probs = keep.get("clip_probs")
+            if clip_probs is not None:
+                outs["tags_probs"] = clip_probs
+                outs["tags"] = probs_to_names(clip_probs, threshold, self.audioset_idx_to_name)
+            return outs
+
     def greedy_search(self, x, sr=None, x_shapes=None, preprocess: bool = True, bos_id: Optional[int] = None,
                       min_pred_size: Optional[int] = None, max_pred_size: Optional[int] = None,
                       forbid_rep_mode: Optional[str] = None) -> Tensor:

@@ -5,6 +5,7 @@
         [--csv_export out.csv] [--precision certified|certified:BASE|bf16|bf16+f16dec|f16|mixed|mixed16|exact|fp32]
         [--sample N --temperature T --top_k K --top_p P --seed S [--consensus ngram|edit --consensus_order K]] [--align]
         [--tag_timeline --tag_window SECONDS --tag_threshold P --tag_off_threshold P --tag_min_duration SECONDS --tag_max_gap SECONDS]
+        [--segments --segment_window SECONDS --segment_hop SECONDS --segment_merge X]
         [--beam_groups G --group_beam W --diversity_penalty L]
         [--prefix "a dog" --ban_words WORD ... --no_repeat_ngram N]
 
@@ -80,6 +81,14 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
                         help="With --tag_timeline: events shorter than this many seconds are dropped (default 0).")
     parser.add_argument("--tag_max_gap", type=float, default=None,
                         help="With --tag_timeline: events of one tag at most this many seconds apart are merged (default 0).")
+    parser.add_argument("--segments", action="store_true",
+                        help="Captions over time for long recordings (CoNeTTEModel.caption_segments): one row per segment with its onset "
+                             "and offset in seconds.  The defaults of the three flags below are untuned.")
+    parser.add_argument("--segment_window", type=float, default=None, help="With --segments: seconds per captioned window (default 10).")
+    parser.add_argument("--segment_hop", type=float, default=None, help="With --segments: seconds between window starts (default 5).")
+    parser.add_argument("--segment_merge", type=float, default=None,
+                        help="With --segments: neighbouring windows whose captions agree at least this much (n-gram F-score, 0 .. 1) "
+                             "form one segment (default 0.5).")
     parser.add_argument("--beam_groups", type=int, default=0,
                         help="G > 0: diverse beam search in G groups (CoNeTTEModel.caption_diverse): G x --group_beam different captions "
                              "per file, one row each, group-major.")
@@ -132,6 +141,22 @@ def get_predict_args(argv: Optional[List[str]] = None) -> Namespace:
         from . import tagging
         tagging.check_arguments(window=tagging.window_frames(args.tag_window), on=args.tag_threshold, off=args.tag_off_threshold,
                                 min_frames=tagging.min_frames(args.tag_min_duration), max_gap=tagging.gap_frames(args.tag_max_gap))
+    seg_flags = ("segment_window", "segment_hop", "segment_merge")
+    if not args.segments and any(getattr(args, k) is not None for k in seg_flags):
+        raise ValueError("--segment_window / --segment_hop / --segment_merge go with --segments")
+    if args.segments:
+        steered = args.prefix is not None or args.ban_words is not None or args.no_repeat_ngram > 0 or args.require_words is not None
+        for flag, on in (("--sample", args.sample > 0), ("--beam_groups", args.beam_groups > 0), ("--align", args.align),
+                         ("--prefix / --ban_words / --no_repeat_ngram / --require_words", steered),
+                         ("--ensemble_models / --ensemble_tasks", args.ensemble_models is not None or args.ensemble_tasks is not None)):
+            if on:
+                raise ValueError(f"--segments runs the plain beam search over windows of a recording; it does not go with {flag}")
+        for k, v in zip(seg_flags, (10.0, 5.0, 0.5)):
+            if getattr(args, k) is None:
+                setattr(args, k, v)
+        from . import segments
+        segments.window_frames(args.segment_window), segments.hop_frames(args.segment_hop)
+        segments.check_arguments(threshold=args.segment_merge)
     if args.beam_groups > 0 and args.sample > 0:
         raise ValueError("--beam_groups searches for different captions; it does not go with --sample")
     if args.beam_groups > 0 and args.align:
@@ -176,6 +201,12 @@ def format_alignment(fpaths: List[str], tasks: List[str], tokenizer, outs: dict)
     tokens, spans = outs["tokens"][:, 0].tolist(), outs["span_time"][:, 0].tolist()
     return [{"audio": osp.basename(f), "task": t, "word": tokenizer.id_to_token(tok), "start": f"{lo:.2f}", "end": f"{hi:.2f}"}
             for f, t, row, sp in zip(fpaths, tasks, tokens, spans) for tok, (lo, hi) in zip(row, sp) if tok not in special]
+
+
+def format_segments(fpaths: List[str], outs: dict) -> List[dict]:
+    """Rows of ``--segments``: one per segment of each file, in time order."""
+    return [{"audio": osp.basename(f), "onset": f"{s['onset']:.2f}", "offset": f"{s['offset']:.2f}", "caption": s["caption"],
+             "lprob": f"{s['lprob']:.4f}"} for f, segs in zip(fpaths, outs["segments"]) for s in segs]
 
 
 def add_tag_events(model, args: Namespace, fpaths: List[str], results: List[dict]) -> None:
@@ -302,6 +333,17 @@ def main_predict(argv: Optional[List[str]] = None) -> List[dict]:
         for f, t, c in zip(fpaths, outs["tasks"], outs["cands"]):
             words = " ".join(f"{r['word']}[{r['start']}-{r['end']}]" for r in results if r["audio"] == osp.basename(f))
             pylog.info(f"File '{osp.basename(f)}' with task '{t}':\n - '{c}'\n - {words}")
+        if args.tag_timeline:
+            add_tag_events(model, args, fpaths, results)
+        if args.csv_export is not None:
+            write_csv(args.csv_export, results)
+        return results
+    if args.segments:     # one row per segment of each file
+        outs = model.caption_segments(fpaths, window_s=args.segment_window, hop_s=args.segment_hop, merge_threshold=args.segment_merge, task=tasks)
+        results = format_segments(fpaths, outs)
+        for f, cut in zip(fpaths, outs["segments_truncated"].tolist()):
+            listed = "\n".join(f" - [{r['onset']}-{r['offset']}] '{r['caption']}'" for r in results if r["audio"] == osp.basename(f))
+            pylog.info(f"File '{osp.basename(f)}' segments{' (more than the 64 kept)' if cut else ''}:\n{listed}")
         if args.tag_timeline:
             add_tag_events(model, args, fpaths, results)
         if args.csv_export is not None:

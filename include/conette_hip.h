@@ -495,6 +495,59 @@ int conette_tag_events(const float* frame_probs, const int32_t* frame_lens, int3
                        int32_t* spans /* (B, n_tags, max_events, 2) */, float* peaks, int32_t* peak_frames /* (B, n_tags, max_events) */,
                        int32_t* counts /* (B, n_tags) */, void* stream);
 
+/* Caption timeline: captions of SPANS of long recordings that were encoded once, and the rule that merges the captions of a
+ * window grid into segments (csrc/dec_spans.h, csrc/dec_segments.h; the CPU statement of the grid and the rule is
+ * conette_amd/segments.py).  conette_decode_spans is conette_decode's beam search over n_spans clips, each a span of one of n_rec
+ * recordings:
+ *   frame_embs : dev (n_rec, t_rec, 768) fp32, conette_encode's output
+ *   spans      : dev (n_spans, 3) int32 rows of (recording, start, len) in frames.  Read on the device by every call (a replayed
+ *                graph follows a table whose contents changed behind the same address) and clamped there -- recording to
+ *                0 .. n_rec - 1, start to 0 .. t_rec - 1, len to 1 .. min(t_span, t_rec - start) -- so that no table makes a kernel
+ *                read out of bounds; checking that a span lies inside its recording's valid frames is the caller's job
+ *   bos_ids    : dev (n_spans) int32       forbid_mask: dev (V) uint8 or NULL
+ *   t_span     : the width of the span axis, at least the longest len
+ *   best_preds (n_spans, max_pred), best_lprobs (n_spans), mult_preds (n_spans, beam, max_pred), mult_lprobs (n_spans, beam),
+ *   out_sizes (2): as conette_decode's, over the n_spans clips.  No trace, margin or step-0 outputs.
+ * Span s is searched exactly as conette_decode searches a clip whose valid frames are frame_embs[rec, start : start + len] with
+ * t_audio = t_span; frames outside a span are never attended.  The precision conversion, the 768 -> 256 projection and the
+ * cross-attention K/V of all layers are computed once per recording FRAME, however many spans hold it (the audio memory carries no
+ * positional encoding), and gathered per span.  Limits as conette_decode's (beam <= 16, max_pred <= 64), n_spans <= 65535.  Works
+ * on decoder-only contexts and in every precision; replayed from the context's decode graph cache like conette_decode.
+ * conette_segments merges windows 0 .. n_windows[r] - 1 (in time order) of recording r into segments, with no context:
+ *   preds      : dev (n_rec, w_max, row_len) int32, the windows' best captions; content = the tokens in front of the first eos_id / pad_id
+ *   n_windows  : dev (n_rec) int32, clamped to 0 .. w_max; windows at or beyond it are never read
+ *   win_spans  : dev (n_rec, w_max, 2) int32 (start, len) in frames      lprobs: dev (n_rec, w_max) fp32
+ *   utility, max_order: conette_consensus's pair utility u; a_k = u(k, k + 1)
+ *   threshold  : finite; window k + 1 joins the run of window k iff a_k >= threshold (fp32)
+ *   max_run    : a run that has reached max_run windows closes anyway; 0: no cap
+ *   max_segments: 1 .. CONETTE_SEG_MAX_SEGMENTS slots per recording, filled in time order
+ *   adjacency  : dev (n_rec, w_max - 1) fp32 or NULL, a_k; exact zeros beyond n_windows - 2
+ *   seg_windows: dev (n_rec, max_segments, 2) int32 (first, end) windows, end exclusive; unused slots (-1, -1)
+ *   seg_frames : dev (n_rec, max_segments, 2) int32 (start, end) frames: the first segment starts at start_0, the last ends at
+ *                start + len of the last window, and two neighbours meet at (start_{k+1} + start_k + len_k + 1) / 2 (floor), k the
+ *                last window of the earlier one; unused slots (-1, -1)
+ *   seg_rep    : dev (n_rec, max_segments) int32, the run's window with the largest lprob (the first on ties; a NaN never wins, the
+ *                first window if all are NaN); unused slots -1
+ *   seg_agree  : dev (n_rec, max_segments) fp32, the smallest a_k inside the run (its bits), 1 for a run of one window; unused slots 0
+ *   counts     : dev (n_rec) int32, the true number of segments, which may exceed max_segments
+ *   workspace  : NULL when `adjacency` is given; otherwise n_rec * (w_max - 1) * 4 bytes
+ * Every element of every output is written by every call; the results equal segments.merge_batch bit for bit.  row_len <= 64,
+ * w_max <= CONETTE_SEG_MAX_WINDOWS.  A failing call of either names the argument (CN_ERR_ARG; a short workspace: CN_ERR_WORKSPACE)
+ * and launches nothing.  Both are asynchronous on `stream`, allocate nothing, are capturable and bit-identical from run to run. */
+#define CONETTE_SEG_MAX_WINDOWS 4096
+#define CONETTE_SEG_MAX_SEGMENTS 256
+size_t conette_decode_spans_workspace_bytes(const conette_ctx* ctx, int32_t n_rec, int32_t t_rec, int32_t n_spans, int32_t t_span,
+                                            int32_t beam, int32_t max_pred);
+int conette_decode_spans(conette_ctx* ctx, const float* frame_embs, const int32_t* spans, const int32_t* bos_ids,
+                         const uint8_t* forbid_mask, int32_t n_rec, int32_t t_rec, int32_t n_spans, int32_t t_span, int32_t beam,
+                         int32_t min_pred, int32_t max_pred, int32_t* best_preds, float* best_lprobs, int32_t* mult_preds,
+                         float* mult_lprobs, int32_t* out_sizes, void* workspace, size_t workspace_bytes, void* stream);
+int conette_segments(const int32_t* preds, const int32_t* n_windows, const int32_t* win_spans, const float* lprobs, int32_t n_rec,
+                     int32_t w_max, int32_t row_len, int32_t utility, int32_t max_order, float threshold, int32_t max_run,
+                     int32_t max_segments, int32_t eos_id, int32_t pad_id, float* adjacency, int32_t* seg_windows,
+                     int32_t* seg_frames, int32_t* seg_rep, float* seg_agree, int32_t* counts, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* a1: torchaudio.functional.resample (preprocessor.py:134-141), sinc_interpolation width 6,
  * rolloff 0.99.  in: dev (rows, n_in) fp32; out: dev (rows, n_out), n_out = ceil(n_in*new/orig). */
 int conette_resample(const float* in, int32_t rows, int32_t n_in, int32_t orig_sr, int32_t new_sr, float* out,
