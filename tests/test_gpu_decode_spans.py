@@ -3,7 +3,8 @@
 
 1. EQUAL TO conette_decode ON GATHERED FRAMES, bit for bit: for every table all five outputs equal Engine.decode on the torch-gathered
    (S, t_span, 768) clips with the spans' lengths.  Both GEMMs of the preparation stay below 4096 rows here, where cn_gemm2 and
-   cn_gemm2_sp dispatch one 64 x 64 tile and a row's sum does not depend on its neighbours.
+   cn_gemm2_sp dispatch one 64 x 64 tile and a row's sum does not depend on its neighbours.  (Above 4096 and 8192 rows, where the
+   tiles change: tests/test_gpu_decoder_rows.py::test_decode_spans_over_8400_frames, against the CPU oracle.)
 2. AGAINST ITSELF, bit for bit: a span alone equals the same span in a table, duplicated spans give duplicated rows, a permuted table
    gives permuted rows, NaNs behind a recording's length and outside every span change nothing, and outputs filled with 0xFF bytes
    are fully overwritten.
